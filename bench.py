@@ -7,9 +7,20 @@
 
 One process per GPU; weak scaling (16 frames per GPU, BASELINE.json configs[1] at N=1).  Prints ONE JSON
 line on rank 0.  `value` = frames all ranks processed / max-over-ranks wall time of exactly K steps, inputs
-resident in HBM.  Extra objects: `roofline` (the DGB dynamic-conv + DFN modulation forward kernel,
-dasr_sean_fwd, timed with HIP events on its own stream inside the timed steps) and `cpu_baseline` (the
-CPU oracle on the host cores, rank 0 at N=1 only, bounded sample).
+resident in HBM; `ms_per_step` = that wall time / K.
+
+A plain run does what this figure needs and nothing else: set-up, W warm-up steps, the K timed steps, the result line.
+`--dump-outputs DIR` then writes what the last timed step computed (see dump_outputs) so that two builds can be
+compared output for output: the inputs are seeded, and the last timed step of such a run starts from the run's starting
+parameters, so the same arguments give the same inputs and, to rounding, the same outputs in every run (the `loss` of
+the result line is then that step's, too).
+
+`--full` adds everything else the benchmark measures or checks, each in passes of its own after the timed region:
+`roofline` (the DGB dynamic-conv + DFN modulation forward kernel, dasr_sean_fwd, timed with HIP events on its launch
+stream: inside the timed steps and in one extra un-overlapped step), `roofline_b32` (the same kernel, forward only at
+batch 32), `roofline_dominant` (the fp32 path's dominant convolution), the bf16 configurations' MFMA roofline, the
+device-side getDepthMask against the host rule, and `cpu_baseline` (the CPU oracle on the host cores, rank 0 at N=1
+only, bounded sample).
 """
 import argparse
 import json
@@ -43,8 +54,14 @@ def parse_args(argv=None):
                     help="A/B: fp32 path without the split-bf16 convolutions (graph.SPLIT_BF16 = False: exact-fp32 MFMA kernels)")
     ap.add_argument("--no-prepack", action="store_true",
                     help="A/B: one launch per packed kernel instead of the two multi-tensor launches per step (graph.PREPACK = False)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-b32", action="store_true", help="skip the forward-only batch-32 roofline pass")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: kernel rooflines (HIP-event timers, one "
+                         "extra un-overlapped step, the forward-only batch-32 pass), device-side depth masks against the host "
+                         "rule, the CPU oracle baseline.  Off by default: a plain run sets up, warms up, times the steps and prints")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
+    ap.add_argument("--no-b32", action="store_true", help="with --full: skip the forward-only batch-32 roofline pass")
     ap.add_argument("--wgrad-stream", action="store_true",
                     help="experiment: weight gradients on a third stream (graph.WGRAD_STREAM; measured slower at c2)")
     ap.add_argument("--serial", action="store_true",
@@ -363,8 +380,43 @@ def cpu_baseline(frames=4, steps=3, max_warmup=5):
                          "/".join("%.1f" % t for t in times), frames / fwd)}
 
 
+DUMP_MAX_ELEMS = 1 << 22      # per array: 4 Mi float32 = 16 MiB
+
+
+def dump_outputs(out_dir, sr, log):
+    """What the caller of the timed path holds after its last timed step, as <out_dir>/<name>.npy:
+
+      sr.npy    float32  the generator's output of that step (the forward of net(lq, depthMap, depthMask), which the training
+                         step feeds to its losses and the inference step returns), flattened in NCHW order; above
+                         DUMP_MAX_ELEMS elements a fixed sample of it (sorted indices drawn once from a generator seeded
+                         with 0, so every run and every build picks the same elements)
+      loss.npy  float64  [l_all, l_pix, l_dynamic], the log optimize_parameters returns (training mode only)
+
+    The inputs are the same in every run, the parameters of the dumped step included: in a training run main() puts the
+    parameters the run started from back in front of the last timed step (the weight-gradient slabs are summed with atomics
+    and Adam turns that rounding noise into +-lr steps, so parameters that went through the earlier steps differ from run to
+    run by far more than rounding: 2.8e-3 on average in sr.npy after 3 + 10 steps).  Measured on MI355X, three runs of one
+    build at c2, 3 + 10 steps: sr.npy bit-identical, loss.npy within 2.4e-7; `--mode infer` is bit-identical as well.
+    """
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    if sr is not None:
+        flat = sr.detach().float().reshape(-1)
+        if flat.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator(device="cpu")
+            g.manual_seed(0)
+            idx = torch.randint(flat.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(out_dir, "sr.npy"), flat.cpu().numpy().astype(np.float32))
+    if log:
+        np.save(os.path.join(out_dir, "loss.npy"),
+                np.array([float(log[k]) for k in ("l_all", "l_pix", "l_dynamic")], dtype=np.float64))
+
+
 def main():
     args = parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be at least 1 and --warmup at least 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args))
 
@@ -450,14 +502,16 @@ def main():
         mk = mk_host
     else:
         mk = prep.depth_to_masks(dm, K_REGIONS)
-        assert torch.equal(mk.cpu(), mk_host), "device-side getDepthMask differs from the host rule"
+        if args.full:
+            assert torch.equal(mk.cpu(), mk_host), "device-side getDepthMask differs from the host rule"
     del mk_host
     object.__setattr__(net, "_bench_inputs", (lq, dm, mk))
 
     timer = SeanTimer()
     timer_conv = ConvTimer()
     timer_split = SplitTimer()
-    if not cpu:
+    extras = args.full and not cpu                 # the kernel timers and the passes after the timed region: --full only
+    if extras:
         timer.install()
         if cfg["dtype"] == "f32":
             timer_split.install()
@@ -481,6 +535,14 @@ def main():
         if rank == 0:
             print("[bench] " + msg, file=sys.stderr, flush=True)
 
+    # --dump-outputs, training: the weight gradients are summed with atomics and Adam turns their rounding noise into +-lr
+    # steps, so after a few steps the parameters of two runs differ by far more than rounding.  The dumped step therefore
+    # starts from the parameters the run started from (one multi-tensor copy in front of the last timed step; the snapshot
+    # is taken here, before the warm-up): what it computes is a function of the seeded inputs and the closed-form fill
+    # alone.  Runs without --dump-outputs do none of this.
+    start_params = None
+    if args.dump_outputs and not infer:
+        start_params = [p.detach().clone() for p in trainer.params]
     note("inputs resident; %d warm-up step(s)" % args.warmup)
     for i in range(args.warmup):
         step()
@@ -489,9 +551,16 @@ def main():
     sync()
     barrier()
     sync()
-    timer.enabled = not cpu
+    timer.enabled = extras
+    last_sr, hook = [], None
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if args.dump_outputs and i == args.steps - 1:
+            if start_params is not None:
+                with torch.no_grad():
+                    torch._foreach_copy_(trainer.params, start_params)
+            if rank == 0:                          # keep the last step's forward output for the dump
+                hook = net.register_forward_hook(lambda _mod, _inp, out: last_sr.append(out.detach()))
         step()
     host_enqueue = time.perf_counter() - t0       # the host has issued every launch of the timed steps (no sync in a step)
     sync()
@@ -505,6 +574,13 @@ def main():
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = el.item()
     loss = float(trainer.log["l_all"]) if not infer else float("nan")
+    if hook is not None:
+        hook.remove()
+    if args.dump_outputs and rank == 0:
+        # (a replayed hipGraph step runs no Python forward: then the log alone is what the caller holds)
+        dump_outputs(args.dump_outputs, last_sr[0] if last_sr else None, None if infer else trainer.log)
+        note("outputs of the last timed step written to %s" % args.dump_outputs)
+    del last_sr
 
     # Roofline of the dynamic-conv forward kernel.  In the timed steps the kernel shares the GPU with the side
     # stream's convolutions (graph.SIDE_STREAM), which stretches its duration and says nothing about the kernel, so
@@ -515,7 +591,7 @@ def main():
     from dasr_amd import graph as _graph
     _side = _graph.SIDE_STREAM
     roof = None
-    if not cpu:
+    if extras:
         _graph.SIDE_STREAM = False
         timer.enabled = True
         timer_split.enabled = True
@@ -563,7 +639,7 @@ def main():
     # (13 launches without / 13 with the residual read); both byte counts are reported: SURVEY §8d's (K mask floats as
     # delivered) and the kernel's true minimum (one region byte).
     roof32 = None
-    if rank == 0 and not cpu and not infer and not args.no_b32 and args.config == "c2":
+    if rank == 0 and extras and not infer and not args.no_b32 and args.config == "c2":
         note("forward-only pass at batch 32 for roofline_b32")
         trainer = None
         net.zero_grad(set_to_none=True)
@@ -612,7 +688,7 @@ def main():
                     pass
         del lq32, dm32, mk32
 
-    if cfg["dtype"] == "bf16" and not cpu:
+    if cfg["dtype"] == "bf16" and extras:
         roof = mfma_roofline(net, args, B, elapsed, timer_conv, args.config)
     # rank 0 alone ran the batch-32 pass: the other ranks wait here, so nobody tears the process group down under it
     barrier()
@@ -627,14 +703,14 @@ def main():
             "vs_baseline": None, "dtype": cfg["dtype"], "data": "synthetic",
             "config": {"workload": cfg["workload"] % B,
                        "global_batch": world * B, "lr_hw": [LR_H, LR_W], "scale": SCALE,
-                       "parallelism": "dp%d" % world, "mode": args.mode, "device": args.device,
+                       "parallelism": "dp%d" % world, "mode": args.mode, "device": args.device, "full": bool(args.full),
                        "hip_graph": bool(use_graph), "arithmetic": arithmetic_note(cfg["dtype"])},
             "loss": round(loss, 6) if loss == loss else None,
             "roofline": roof,
             "roofline_b32": roof32,
             "roofline_dominant": timer_split.summary(),
         }
-        if world == 1 and not cpu and not infer and not args.no_cpu_baseline and args.config == "c2":
+        if world == 1 and extras and not infer and not args.no_cpu_baseline and args.config == "c2":
             note("GPU part done (%.1f ms/step); timing the CPU oracle baseline" % (1e3 * elapsed / args.steps))
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)

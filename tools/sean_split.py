@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Split the k_sean_fwd_onehot dispatches of a `rocprofv3 --kernel-trace -- python3 bench.py ...` run by the phase of
+"""Split the k_sean_fwd_onehot dispatches of a `rocprofv3 --kernel-trace -- python3 bench.py --full ...` run by the phase of
 bench.py they belong to, so that profiles/ can reproduce bench.py's roofline numbers from tracked files:
 
   phase A  warm-up + timed steps      26 launches per step, co-running with the side-stream convolutions (B=16)
@@ -50,7 +50,7 @@ def summarise(sel, B):
     return out
 
 
-res = {"source": "rocprofv3 --kernel-trace -- python3 bench.py --warmup %d --steps %d (%s)" % (warmup, steps, os.path.basename(csvs[0])),
+res = {"source": "rocprofv3 --kernel-trace -- python3 bench.py --full --warmup %d --steps %d (%s)" % (warmup, steps, os.path.basename(csvs[0])),
        "kernel": "k_sean_fwd_onehot", "dispatches": len(dur)}
 for name, sel in phases.items():
     res[name] = summarise(sel, 32 if name.endswith("b32") else 16)
