@@ -1163,9 +1163,10 @@ __global__ void __launch_bounds__(512) k_sean_bwd_a_onehot(
     }
 }
 
-__global__ void __launch_bounds__(256) k_sean_dD_reduce(const float* __restrict__ slabs, const int* __restrict__ flag,
-                                                        float* __restrict__ dD, int per_sample, int nslab, size_t n) {
-    if (flag && *flag != 0) return;
+// (the one-hot and the soft-mask pass A write the same slab layout and the device flag lets exactly one of them work: this
+// kernel sums whichever slabs were written)
+__global__ void __launch_bounds__(256) k_sean_dD_reduce(const float* __restrict__ slabs, float* __restrict__ dD,
+                                                        int per_sample, int nslab, size_t n) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         size_t b = i / per_sample, e = i % per_sample;
         const float* p = slabs + b * (size_t)nslab * per_sample + e;
@@ -1175,6 +1176,365 @@ __global__ void __launch_bounds__(256) k_sean_dD_reduce(const float* __restrict_
     }
 }
 
+// =====================================================================================================
+// Soft (non one-hot) masks: the dynamic convolution as a dense GEMM on the exact-fp32 matrix cores.
+//
+//     [gamma1 | beta1][p, 0:2C] = A[p, r] . D[b][r, 0:2C],   r = tap*K + k,  A[p, r] = mask[b, k, p + tap]  (0 outside the image)
+//     dD[b][r, 0:2C]            = A^T . [a_g*dgamma | a_b*dbeta]                 (reduction over the sample's pixels)
+//
+// v_mfma_f32_32x32x2_f32 is bitwise an fmaf chain in contraction order, so gamma1 / beta1 are summed in the order of the
+// scalar general kernel (tap outer, region inner, bias afterwards) with no `mask != 0` shortcut.  Workgroup = 4 waves, tile =
+// SEAN_TH rows x 32 columns x one 64-channel slice, persistent over the tiles of ONE sample (D[b] is staged once).  The 128
+// gamma|beta columns are dealt to the waves in 32-column blocks (wave w: gamma for w < 2, beta otherwise; channels 32*(w&1)..).
+// Per tile row (32 pixels) a wave runs ceil(9K/2) MFMAs - A is one LDS read of the mask tile per lane, B one LDS read of the
+// staged D - then the accumulator block goes through LDS ([32 pixels][128 columns]) so that the modulation runs in the lane
+// layout of the one-hot kernels: 16 lanes x float4 = the 64 channels of a pixel, 1 KiB contiguous per wave instruction.
+// Odd 9K: the last step's second operand pair is zero (a guarded load, never an out-of-range read).
+// =====================================================================================================
+#define SS_GST 132            // pixel stride of the transposed accumulator tile in floats (128 columns + 4: 16-byte rows)
+#define SS_MAXMB 5            // ceil(9 * SEAN_MAXK / 32) row blocks of dD
+__host__ __device__ constexpr int sean_soft_off_ints(int K) { return ((9 * K + 1) / 2 * 2 + 3) / 4 * 4; }
+// LDS floats: D [18K][64] | mask tile [K][TH+2][TW+2] | operand offsets | [32][SS_GST] row tile (backward: two of them and
+// the scratch of the per-channel sums).  Forward 77 KB at K = 10 (two workgroups per CU), 112 KB at K = 16; backward 130 KB at
+// K = 16.
+__host__ __device__ constexpr int sean_soft_lds_bytes(int K, bool bwd) {
+    return 4 * (18 * K * 64 + K * (SEAN_TH + 2) * (SEAN_TW + 2) + sean_soft_off_ints(K) + (bwd ? 2 : 1) * 32 * SS_GST +
+                (bwd ? 4 * 18 * 16 : 0));
+}
+struct SeanSoftLds { float* sD; float* sM; int* sOff; float* sG; float* sred; };
+__device__ __forceinline__ SeanSoftLds sean_soft_carve(char* smem, int K) {
+    SeanSoftLds l;
+    l.sD = (float*)smem;
+    l.sM = l.sD + 18 * K * 64;
+    l.sOff = (int*)(l.sM + sean_lds_M_floats(K));
+    l.sG = (float*)(l.sOff + sean_soft_off_ints(K));
+    l.sred = l.sG + 2 * 32 * SS_GST;                 // (backward only)
+    return l;
+}
+// D[b], channel slice [c0, c0 + 64) as [18K][64] (zero beyond C; C % 4 == 0), and the mask-tile offset of every
+// contraction index r = tap*K + k:  (k*MH + dy)*MW + dx
+__device__ __forceinline__ void sean_soft_stage_D(const SeanGeom& g, const float* __restrict__ D, const SeanSoftLds& l, int b,
+                                                  int c0) {
+    const int rows = 18 * g.K;
+    for (int i = threadIdx.x; i < rows * 16; i += blockDim.x) {
+        const int q = i & 15, r = i >> 4, c = c0 + 4 * q;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (c + 3 < g.C) v = *(const float4*)(D + ((size_t)b * rows + r) * g.C + c);
+        *(float4*)(l.sD + r * 64 + 4 * q) = v;
+    }
+    const int MW = SEAN_TW + 2, MH = SEAN_TH + 2;
+    for (int i = threadIdx.x; i < sean_soft_off_ints(g.K); i += blockDim.x) {
+        const int tap = i / g.K, k = i - tap * g.K;
+        l.sOff[i] = i < 9 * g.K ? (k * MH + tap / 3) * MW + tap % 3 : 0;
+    }
+}
+// mask tile with a 1-pixel halo, zero outside the image
+__device__ __forceinline__ void sean_soft_stage_M(const SeanGeom& g, const float* __restrict__ mask, float* sM, int b, int y0,
+                                                  int x0) {
+    const int MW = SEAN_TW + 2, MH = SEAN_TH + 2;
+    const int nM = g.K * MH * MW;
+    for (int i = threadIdx.x; i < nM; i += blockDim.x) {
+        const int xx = i % MW, yy = (i / MW) % MH, k = i / (MW * MH);
+        const int gy = y0 + yy - 1, gx = x0 + xx - 1;
+        float v = 0.f;
+        if (gy >= 0 && gy < g.H && gx >= 0 && gx < g.W) v = mask[(((size_t)b * g.K + k) * g.H + gy) * g.W + gx];
+        sM[i] = v;
+    }
+}
+// One wave's 32 pixels (tile row ly) x 32 columns of gamma1|beta1 (no bias).  sDw: the wave's column of the staged D
+// (row stride 64), already offset by the lane's column; called under wave-uniform conditions only.
+__device__ __forceinline__ f32x16 sean_soft_gemm(const SeanSoftLds& l, const float* sDw, int K, int ly, int lane) {
+    const int NR = 9 * K, NS = (NR + 1) / 2, hi = lane >> 5;
+    const float* am = l.sM + ly * (SEAN_TW + 2) + (lane & 31);
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll 4
+    for (int step = 0; step < NS; ++step) {
+        const int idx = 2 * step + hi;
+        float a = 0.f, bv = 0.f;
+        if (idx < NR) {
+            a = am[l.sOff[idx]];
+            bv = sDw[idx * 64];
+        }
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bv, acc, 0, 0, 0);
+    }
+    return acc;
+}
+// accumulator block -> [32 pixels][SS_GST] tile: register r of lane l is pixel (r&3) + 8*(r>>2) + 4*(l>>5), column l&31
+__device__ __forceinline__ void sean_soft_put(float* sGb, const f32x16& acc, int colblk, int lane) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) sGb[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * SS_GST + 32 * colblk + (lane & 31)] = acc[r];
+}
+
+template <bool RELU, bool HAS_RES, typename T>
+__global__ void __launch_bounds__(256) k_sean_fwd_soft(SeanGeom g, const T* __restrict__ t, const float* __restrict__ mean,
+                                                       const float* __restrict__ var, const T* __restrict__ gb2,
+                                                       const float* __restrict__ mask, const float* __restrict__ D,
+                                                       const float* __restrict__ bias_g, const float* __restrict__ bias_b,
+                                                       const float* __restrict__ alpha_g, const float* __restrict__ alpha_b,
+                                                       const T* __restrict__ residual, T* __restrict__ out, float eps,
+                                                       int ntiles, const int* __restrict__ onehot_flag) {
+    if (onehot_flag && *onehot_flag == 0) return;   // one-hot masks: k_sean_fwd_onehot does the work
+    DASR_DYN_SMEM(smem);
+    const SeanSoftLds l = sean_soft_carve(smem, g.K);
+    const int b = blockIdx.y, c0 = blockIdx.z * 64;
+    const int tiles_x = (g.W + SEAN_TW - 1) / SEAN_TW;
+    const int lane = threadIdx.x & 63, wv = DASR_UNIFORM((int)(threadIdx.x >> 6));
+    const bool blk_live = c0 + 32 * (wv & 1) < g.C;           // wave-uniform: a column block beyond C is never computed
+    const float* sDw = l.sD + (wv >> 1) * 9 * g.K * 64 + 32 * (wv & 1) + (lane & 31);
+    const int cq = lane & 15, ps = lane >> 4;
+    const bool live = c0 + 4 * cq < g.C;
+    const int c = live ? c0 + 4 * cq : 0;                     // dead lanes shadow channel 0 and never store
+    const float a_g = alpha_g[0], a_b = alpha_b[0];
+    const float4 mu = *(const float4*)(mean + (size_t)b * g.C + c);
+    const float4 vr = *(const float4*)(var + (size_t)b * g.C + c);
+    const float4 sc = make_float4(dasr_double_in_scale(vr.x, eps), dasr_double_in_scale(vr.y, eps),
+                                  dasr_double_in_scale(vr.z, eps), dasr_double_in_scale(vr.w, eps));
+    const float4 bg = *(const float4*)(bias_g + c), bb = *(const float4*)(bias_b + c);
+    sean_soft_stage_D(g, D, l, b, c0);
+    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int x0 = (tile % tiles_x) * SEAN_TW, y0 = (tile / tiles_x) * SEAN_TH;
+        __syncthreads();                                      // the previous tile is done with sM
+        sean_soft_stage_M(g, mask, l.sM, b, y0, x0);
+        __syncthreads();
+        for (int ly = 0; ly < SEAN_TH; ++ly) {
+            const int y = y0 + ly;
+            if (y >= g.H) break;                              // (the same for every thread of the workgroup)
+            // this thread's two pixels of the row: requested before the matrix loop, consumed after it
+            float4 tv[2], g2[2], b2[2], rv[2];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int x = imin(x0 + 16 * u + 4 * wv + ps, g.W - 1);
+                const size_t p = ((size_t)b * g.H + y) * g.W + x;
+                tv[u] = ld4(t + p * g.C + c);
+                g2[u] = ld4(gb2 + p * 2 * g.C + c);
+                b2[u] = ld4(gb2 + p * 2 * g.C + g.C + c);
+                if (HAS_RES) rv[u] = ld4(residual + p * g.C + c);
+            }
+            float* sGb = l.sG;
+            if (blk_live) sean_soft_put(sGb, sean_soft_gemm(l, sDw, g.K, ly, lane), wv, lane);
+            __syncthreads();
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int lx = 16 * u + 4 * wv + ps, x = x0 + lx;
+                if (!(live && x < g.W)) continue;
+                const size_t p = ((size_t)b * g.H + y) * g.W + x;
+                const float4 r1 = *(const float4*)(sGb + lx * SS_GST + 4 * cq);
+                const float4 r2 = *(const float4*)(sGb + lx * SS_GST + 64 + 4 * cq);
+                const float g1[4] = {r1.x + bg.x, r1.y + bg.y, r1.z + bg.z, r1.w + bg.w};
+                const float b1[4] = {r2.x + bb.x, r2.y + bb.y, r2.z + bb.z, r2.w + bb.w};
+                const float tq[4] = {tv[u].x, tv[u].y, tv[u].z, tv[u].w}, g2q[4] = {g2[u].x, g2[u].y, g2[u].z, g2[u].w};
+                const float b2q[4] = {b2[u].x, b2[u].y, b2[u].z, b2[u].w};
+                const float muq[4] = {mu.x, mu.y, mu.z, mu.w}, scq[4] = {sc.x, sc.y, sc.z, sc.w};
+                const float rq[4] = {HAS_RES ? rv[u].x : 0.f, HAS_RES ? rv[u].y : 0.f, HAS_RES ? rv[u].z : 0.f,
+                                     HAS_RES ? rv[u].w : 0.f};
+                float o[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float gam = a_g * g1[j] + (1.f - a_g) * g2q[j];
+                    const float bet = a_b * b1[j] + (1.f - a_b) * b2q[j];
+                    const float xh = (tq[j] - muq[j]) * scq[j];
+                    o[j] = xh * (1.f + gam) + bet;
+                    if (HAS_RES) o[j] += rq[j];
+                    if (RELU) o[j] = o[j] > 0.f ? o[j] : 0.f;
+                }
+                st4(out + p * g.C + c, make_float4(o[0], o[1], o[2], o[3]));
+            }
+            __syncthreads();                                  // the row tile is free again
+        }
+    }
+}
+
+// Backward pass A for soft masks.  Per tile row: gamma1|beta1 recomputed with the forward's MFMA loop (tile 0 of sG), the
+// elementwise part of k_sean_bwd_a in the float4 lane layout, [a_g*dgamma | a_b*dbeta] of the row into tile 1 of sG (zero
+// for pixels outside the image and channels beyond C), then dD[r, 32 columns of the wave] += A^T . dG with the pixel as the
+// contraction index: ceil(9K/32) accumulator blocks of 32 rows per wave, resident in registers for the workgroup's whole
+// pixel range.  Each workgroup writes its dD as a slab [18][K][C]; k_sean_dD_reduce sums the slabs in a fixed order - no
+// atomics on dD, no LDS tables of its size.
+template <typename T>
+__global__ void __launch_bounds__(256) k_sean_bwd_a_soft(
+    SeanGeom g, const T* __restrict__ dout, const T* __restrict__ out, const T* __restrict__ t,
+    const float* __restrict__ mean, const float* __restrict__ var, const T* __restrict__ gb2,
+    const float* __restrict__ mask, const float* __restrict__ D, const float* __restrict__ bias_g,
+    const float* __restrict__ bias_b, const float* __restrict__ alpha_g, const float* __restrict__ alpha_b,
+    T* __restrict__ dt, T* __restrict__ dgb2, float* __restrict__ dD_slabs, float* __restrict__ dbias_g,
+    float* __restrict__ dbias_b, float* __restrict__ dalpha_g, float* __restrict__ dalpha_b, T* __restrict__ dres,
+    float* __restrict__ S, int relu, float eps, int ntiles, const int* __restrict__ onehot_flag) {
+    if (onehot_flag && *onehot_flag == 0) return;   // one-hot masks: k_sean_bwd_a_onehot does the work
+    DASR_DYN_SMEM(smem);
+    const SeanSoftLds l = sean_soft_carve(smem, g.K);
+    float* sG1 = l.sG;                               // gamma1 | beta1 of the row
+    float* sdG = l.sG + 32 * SS_GST;                 // a_g*dgamma | a_b*dbeta of the row
+    const int b = blockIdx.y, c0 = blockIdx.z * 64;
+    const int tiles_x = (g.W + SEAN_TW - 1) / SEAN_TW;
+    const int MW = SEAN_TW + 2, MH = SEAN_TH + 2;
+    const int lane = threadIdx.x & 63, wv = DASR_UNIFORM((int)(threadIdx.x >> 6));
+    const int NR = 9 * g.K, MB = (NR + 31) / 32;     // rows of dD per half, their 32-row blocks
+    const bool blk_live = c0 + 32 * (wv & 1) < g.C;
+    const float* sDw = l.sD + (wv >> 1) * NR * 64 + 32 * (wv & 1) + (lane & 31);
+    const int cq = lane & 15, ps = lane >> 4, hi = lane >> 5;
+    const bool live = c0 + 4 * cq < g.C;
+    const int c = live ? c0 + 4 * cq : 0;
+    const float a_g = alpha_g[0], a_b = alpha_b[0];
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 mu = *(const float4*)(mean + (size_t)b * g.C + c);
+    const float4 vr = *(const float4*)(var + (size_t)b * g.C + c);
+    const float4 sc = make_float4(dasr_double_in_scale(vr.x, eps), dasr_double_in_scale(vr.y, eps),
+                                  dasr_double_in_scale(vr.z, eps), dasr_double_in_scale(vr.w, eps));
+    const float4 bg = *(const float4*)(bias_g + c), bb = *(const float4*)(bias_b + c);
+    // A^T operand of the dD product: this lane's row of block mb is r = 32*mb + (lane&31); its mask-tile offset, or -1
+    int aoff[SS_MAXMB];
+#pragma unroll
+    for (int mb = 0; mb < SS_MAXMB; ++mb) {
+        const int r = 32 * mb + (lane & 31), tap = r / g.K, k = r - tap * g.K;
+        aoff[mb] = r < NR ? (k * MH + tap / 3) * MW + tap % 3 : -1;
+    }
+    f32x16 acc[SS_MAXMB];
+#pragma unroll
+    for (int mb = 0; mb < SS_MAXMB; ++mb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[mb][r] = 0.f;
+    float S1[4] = {0.f, 0.f, 0.f, 0.f}, S2[4] = {0.f, 0.f, 0.f, 0.f}, dbg[4] = {0.f, 0.f, 0.f, 0.f},
+          dbb[4] = {0.f, 0.f, 0.f, 0.f};
+    float dag = 0.f, dab = 0.f;
+    sean_soft_stage_D(g, D, l, b, c0);
+    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int x0 = (tile % tiles_x) * SEAN_TW, y0 = (tile / tiles_x) * SEAN_TH;
+        __syncthreads();                                      // the previous tile is done with sM and the two row tiles
+        sean_soft_stage_M(g, mask, l.sM, b, y0, x0);
+        __syncthreads();
+        for (int ly = 0; ly < SEAN_TH; ++ly) {
+            const int y = y0 + ly;
+            if (y >= g.H) break;
+            float4 g0v[2], ov[2], tv[2], g2[2], b2[2];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int x = imin(x0 + 16 * u + 4 * wv + ps, g.W - 1);
+                const size_t p = ((size_t)b * g.H + y) * g.W + x;
+                g0v[u] = ld4(dout + p * g.C + c);
+                ov[u] = ld4(out + p * g.C + c);
+                tv[u] = ld4(t + p * g.C + c);
+                g2[u] = ld4(gb2 + p * 2 * g.C + c);
+                b2[u] = ld4(gb2 + p * 2 * g.C + g.C + c);
+            }
+            if (blk_live) sean_soft_put(sG1, sean_soft_gemm(l, sDw, g.K, ly, lane), wv, lane);
+            __syncthreads();                                  // sG1 complete; the previous row's dD product has read sdG
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int lx = 16 * u + 4 * wv + ps, x = x0 + lx;
+                float4 G1 = zero4, B1 = zero4;
+                if (live && x < g.W) {
+                    const size_t p = ((size_t)b * g.H + y) * g.W + x;
+                    const float4 r1 = *(const float4*)(sG1 + lx * SS_GST + 4 * cq);
+                    const float4 r2 = *(const float4*)(sG1 + lx * SS_GST + 64 + 4 * cq);
+                    const float g1q[4] = {r1.x + bg.x, r1.y + bg.y, r1.z + bg.z, r1.w + bg.w};
+                    const float b1q[4] = {r2.x + bb.x, r2.y + bb.y, r2.z + bb.z, r2.w + bb.w};
+                    const float g0q[4] = {g0v[u].x, g0v[u].y, g0v[u].z, g0v[u].w}, oq[4] = {ov[u].x, ov[u].y, ov[u].z, ov[u].w};
+                    const float tq[4] = {tv[u].x, tv[u].y, tv[u].z, tv[u].w}, g2q[4] = {g2[u].x, g2[u].y, g2[u].z, g2[u].w};
+                    const float b2q[4] = {b2[u].x, b2[u].y, b2[u].z, b2[u].w};
+                    const float muq[4] = {mu.x, mu.y, mu.z, mu.w}, scq[4] = {sc.x, sc.y, sc.z, sc.w};
+                    float g0[4], dg2[4], db2[4], dg1[4], db1[4], dxh[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        g0[j] = g0q[j];
+                        if (relu && !(oq[j] > 0.f)) g0[j] = 0.f;
+                        const float gam = a_g * g1q[j] + (1.f - a_g) * g2q[j];
+                        const float xc = tq[j] - muq[j];
+                        const float xh = xc * scq[j];
+                        const float dgam = g0[j] * xh, dbet = g0[j];
+                        dg2[j] = (1.f - a_g) * dgam;
+                        db2[j] = (1.f - a_b) * dbet;
+                        dag = fmaf(dgam, g1q[j] - g2q[j], dag);
+                        dab = fmaf(dbet, b1q[j] - b2q[j], dab);
+                        dg1[j] = a_g * dgam;
+                        db1[j] = a_b * dbet;
+                        dbg[j] += dg1[j];
+                        dbb[j] += db1[j];
+                        dxh[j] = g0[j] * (1.f + gam);
+                        S1[j] += dxh[j];
+                        S2[j] = fmaf(dxh[j], xc, S2[j]);
+                    }
+                    if (dres) st4(dres + p * g.C + c, make_float4(g0[0], g0[1], g0[2], g0[3]));
+                    st4(dgb2 + p * 2 * g.C + c, make_float4(dg2[0], dg2[1], dg2[2], dg2[3]));
+                    st4(dgb2 + p * 2 * g.C + g.C + c, make_float4(db2[0], db2[1], db2[2], db2[3]));
+                    st4(dt + p * g.C + c, make_float4(dxh[0], dxh[1], dxh[2], dxh[3]));
+                    G1 = make_float4(dg1[0], dg1[1], dg1[2], dg1[3]);
+                    B1 = make_float4(db1[0], db1[1], db1[2], db1[3]);
+                }
+                *(float4*)(sdG + lx * SS_GST + 4 * cq) = G1;
+                *(float4*)(sdG + lx * SS_GST + 64 + 4 * cq) = B1;
+            }
+            __syncthreads();                                  // sdG complete; everybody has read sG1
+            if (blk_live) {
+                // dD block += A^T . dG: lane = (row 32*mb + (lane&31), pixel 2*step + hi) of A^T, (pixel, column lane&31) of dG
+                const float* am = l.sM + ly * MW + hi;
+                const float* gq = sdG + hi * SS_GST + 32 * wv + (lane & 31);
+#pragma unroll 2
+                for (int step = 0; step < 16; ++step) {
+                    const float bv = gq[2 * step * SS_GST];
+#pragma unroll
+                    for (int mb = 0; mb < SS_MAXMB; ++mb) {
+                        if (mb < MB) {                        // (wave-uniform: K is a kernel argument)
+                            const float a = aoff[mb] >= 0 ? am[aoff[mb] + 2 * step] : 0.f;
+                            acc[mb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bv, acc[mb], 0, 0, 0);
+                        }
+                    }
+                }
+            }
+        }
+    }
+    // ---- per-channel sums: over the 4 pixel sub-lanes (lanes l, l+16, l+32, l+48), then over the 4 waves
+    float vals[18] = {S1[0], S1[1], S1[2], S1[3], S2[0], S2[1], S2[2], S2[3], dbg[0], dbg[1], dbg[2], dbg[3],
+                      dbb[0], dbb[1], dbb[2], dbb[3], dag, dab};
+#pragma unroll
+    for (int q = 0; q < 18; ++q) {
+        vals[q] += __shfl_xor(vals[q], 16, 64);
+        vals[q] += __shfl_xor(vals[q], 32, 64);
+    }
+    if (ps == 0) {
+#pragma unroll
+        for (int q = 0; q < 18; ++q) l.sred[(wv * 18 + q) * 16 + cq] = vals[q];
+    }
+    __syncthreads();
+    if (wv == 0 && ps == 0) {
+        float r[18];
+#pragma unroll
+        for (int q = 0; q < 18; ++q) {
+            r[q] = 0.f;
+            for (int w = 0; w < 4; ++w) r[q] += l.sred[(w * 18 + q) * 16 + cq];
+        }
+        if (live) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                atomicAdd(&S[((size_t)b * g.C + c + j) * 2 + 0], r[j]);
+                atomicAdd(&S[((size_t)b * g.C + c + j) * 2 + 1], r[4 + j]);
+                atomicAdd(&dbias_g[c + j], r[8 + j]);
+                atomicAdd(&dbias_b[c + j], r[12 + j]);
+            }
+        }
+        float ra = live ? r[16] : 0.f, rb = live ? r[17] : 0.f;
+        for (int off = 8; off > 0; off >>= 1) {
+            ra += __shfl_xor(ra, off, 64);
+            rb += __shfl_xor(rb, off, 64);
+        }
+        if (cq == 0) {
+            atomicAdd(dalpha_g, ra);
+            atomicAdd(dalpha_b, rb);
+        }
+    }
+    // ---- slab [b][blockIdx.x][18][K][C] (a workgroup without tiles writes zeros: the reduction reads every slab)
+    float* slab = dD_slabs + ((size_t)b * gridDim.x + blockIdx.x) * 18 * g.K * g.C;
+    const int cc = c0 + 32 * (wv & 1) + (lane & 31);
+#pragma unroll
+    for (int mb = 0; mb < SS_MAXMB; ++mb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = 32 * mb + (r & 3) + 8 * (r >> 2) + 4 * hi;
+            if (row < NR && cc < g.C) slab[((size_t)(wv >> 1) * NR + row) * g.C + cc] = acc[mb][r];
+        }
+}
+
 // ------------------------------------------------------------------------------------------ host side
 static int sean_bwd_blocks_per_sample(int B, int H, int W) {
     int ntiles = ((W + SF_TW - 1) / SF_TW) * ((H + 4 - 1) / 4);
@@ -1182,6 +1542,17 @@ static int sean_bwd_blocks_per_sample(int B, int H, int W) {
     if (n < 1) n = 1;
     if (n > ntiles) n = ntiles;
     return n;
+}
+
+// LDS bytes of the scalar general backward kernel (C % 4 != 0 only): D tables + mask tile + dD accumulators + reduction scratch
+static size_t sean_bwd_general_lds(int K) {
+    return sizeof(float) * (size_t)(2 * (2 * 9 * K * 64) + K * (SEAN_TH + 2) * (SEAN_TW + 2) + 6 * 256);
+}
+// ... which keeps two [2][9][K][64] tables in the CU's 160 KB of LDS: K <= 14
+static int sean_general_max_regions(void) {
+    int k = SEAN_MAXK;
+    while (k > 1 && sean_bwd_general_lds(k) > 160 * 1024) --k;
+    return k;
 }
 
 template <typename T>
@@ -1228,7 +1599,23 @@ static int sean_fwd_impl(const T* t, const float* mean, const float* var, const 
         else      { if (residual) SEAN_FWD_GO(false, true); else SEAN_FWD_GO(false, false); }
 #undef SEAN_FWD_GO
     }
-    if (!fast_only) {
+    if (!fast_only && (C % 4) == 0) {
+        // soft masks (or no region bytes): the MFMA kernel, persistent over the tiles of one (sample, slice)
+        const int ntiles = ((W + SEAN_TW - 1) / SEAN_TW) * ((H + SEAN_TH - 1) / SEAN_TH);
+        const int slices = (int)dasr_cdiv(C, 64);
+        int nblk = (512 + B * slices - 1) / (B * slices);      // 256 CUs x 2 resident workgroups at K <= 10
+        if (nblk > ntiles) nblk = ntiles;
+        const size_t lds = (size_t)sean_soft_lds_bytes(K, false);
+        const int* fl = fast ? onehot_flag : (const int*)nullptr;
+#define SEAN_SOFT_GO(RELU, RES)                                                                                       \
+    DASR_LAUNCH((k_sean_fwd_soft<RELU, RES, T>), dim3(nblk, B, slices), dim3(256), lds, stream, g, t, mean, var, gb2, \
+                mask, D, bias_g, bias_b, alpha_g, alpha_b, residual, out, eps, ntiles, fl)
+        if (relu) { if (residual) SEAN_SOFT_GO(true, true); else SEAN_SOFT_GO(true, false); }
+        else      { if (residual) SEAN_SOFT_GO(false, true); else SEAN_SOFT_GO(false, false); }
+#undef SEAN_SOFT_GO
+    } else if (!fast_only) {
+        // C % 4 != 0: the scalar general kernels (K <= 14, the bound of their backward)
+        if (K > sean_general_max_regions()) return DASR_E_UNSUPPORTED;
         int tiles = ((W + SEAN_TW - 1) / SEAN_TW) * ((H + SEAN_TH - 1) / SEAN_TH);
         size_t lds = sizeof(float) * (size_t)(2 * 9 * K * 64 + K * (SEAN_TH + 2) * (SEAN_TW + 2));
         DASR_LAUNCH((k_sean_fwd<T>), dim3(tiles, B, dasr_cdiv(C, 64)), dim3(256), lds, stream, g, t, mean, var, gb2, mask, D,
@@ -1268,16 +1655,12 @@ __global__ void __launch_bounds__(256) k_sean_bwd_zero(float* __restrict__ S, in
     else if (i == nS + 2 * C + 1) dab[0] = 0.f;
 }
 
-// LDS bytes of the general (soft-mask) backward kernel: D tables + mask tile + dD accumulators + reduction scratch
-static size_t sean_bwd_general_lds(int K) {
-    return sizeof(float) * (size_t)(2 * (2 * 9 * K * 64) + K * (SEAN_TH + 2) * (SEAN_TW + 2) + 6 * 256);
-}
-// Largest region count the soft-mask kernels take forward AND backward (the backward keeps two [2][9][K][64] tables in
-// the CU's 160 KB of LDS: K <= 14); one-hot masks go up to SEAN_MAXK = 16.
+// Largest region count the soft-mask kernels take forward AND backward: SEAN_MAXK = 16, as for one-hot masks (the MFMA
+// kernels keep dD in accumulator registers; 130 KB of LDS at K = 16).  Only the scalar fallback for C % 4 != 0 is still
+// bounded by its LDS tables (sean_general_max_regions() = 14).
 extern "C" int dasr_sean_soft_mask_max_regions(void) {
-    int k = SEAN_MAXK;
-    while (k > 1 && sean_bwd_general_lds(k) > 160 * 1024) --k;
-    return k;
+    static_assert(sean_soft_lds_bytes(SEAN_MAXK, true) <= 160 * 1024, "soft-mask backward LDS");
+    return SEAN_MAXK;
 }
 
 extern "C" size_t dasr_sean_bwd_workspace(int B, int H, int W, int C, int K) {
@@ -1310,13 +1693,15 @@ static int sean_bwd_impl(const T* dout, const T* out, const T* t, const float* m
     float* slabs = S + 2 * (size_t)B * C;
     const bool fast = region != nullptr && (C % 4) == 0;
     const bool fast_only = fast && onehot_flag == nullptr;
-    if (!fast_only && K > dasr_sean_soft_mask_max_regions()) return DASR_E_UNSUPPORTED;
+    const bool soft = !fast_only && (C % 4) == 0;            // MFMA soft-mask kernel; otherwise (C % 4 != 0) the scalar one
+    const bool scalar = !fast_only && !soft;
+    if (scalar && K > sean_general_max_regions()) return DASR_E_UNSUPPORTED;
     // the accumulators the kernels add into with atomics: one launch instead of five memsets; dD is only accumulated
-    // into by the general kernel (the one-hot path overwrites all of it in k_sean_dD_reduce)
+    // into by the scalar kernel (the slab paths overwrite all of it in k_sean_dD_reduce)
     (void)st;
     DASR_LAUNCH(k_sean_bwd_zero, dim3(dasr_cdiv((size_t)2 * B * C + 2 * C + 2, 256)), dim3(256), 0, stream, S, 2 * B * C,
                 dbias_g, dbias_b, C, dalpha_g, dalpha_b);
-    if (!fast_only) {
+    if (scalar) {
         hipError_t e = hipMemsetAsync(dD, 0, sizeof(float) * (size_t)B * 18 * K * C, st);
         if (e != hipSuccess) return (int)e;
     }
@@ -1350,11 +1735,22 @@ static int sean_bwd_impl(const T* dout, const T* out, const T* t, const float* m
             DASR_LAUNCH((k_sean_bwd_a_onehot<T, TH_SMALL>), dim3(nblk, B, dasr_cdiv(C, 64)), dim3(512), lds, stream, g, dout, out, t,
                         mean, var, gb2, region, onehot_flag, D, bias_g, bias_b, alpha_g, alpha_b, dt, dgb2, slabs, dbias_g,
                         dbias_b, dalpha_g, dalpha_b, dres, S, relu, eps, ntiles, (float*)nullptr);
-        size_t n = (size_t)B * 18 * K * C;
-        DASR_LAUNCH(k_sean_dD_reduce, dim3(dasr_ew_grid(n)), dim3(256), 0, stream, (const float*)slabs, onehot_flag, dD,
-                    18 * K * C, nblk, n);
     }
-    if (!fast_only) {
+    if (soft) {
+        // same grid and slab layout as the one-hot pass A (a workgroup beyond the tile count writes a zero slab)
+        const int nblk = sean_bwd_blocks_per_sample(B, H, W);
+        const int ntiles = ((W + SEAN_TW - 1) / SEAN_TW) * ((H + SEAN_TH - 1) / SEAN_TH);
+        DASR_LAUNCH((k_sean_bwd_a_soft<T>), dim3(nblk, B, dasr_cdiv(C, 64)), dim3(256), (size_t)sean_soft_lds_bytes(K, true),
+                    stream, g, dout, out, t, mean, var, gb2, mask, D, bias_g, bias_b, alpha_g, alpha_b, dt, dgb2, slabs,
+                    dbias_g, dbias_b, dalpha_g, dalpha_b, dres, S, relu, eps, ntiles,
+                    fast ? onehot_flag : (const int*)nullptr);
+    }
+    if (fast || soft) {
+        size_t n = (size_t)B * 18 * K * C;
+        DASR_LAUNCH(k_sean_dD_reduce, dim3(dasr_ew_grid(n)), dim3(256), 0, stream, (const float*)slabs, dD, 18 * K * C,
+                    sean_bwd_blocks_per_sample(B, H, W), n);
+    }
+    if (scalar) {
         int tiles = ((W + SEAN_TW - 1) / SEAN_TW) * ((H + SEAN_TH - 1) / SEAN_TH);
         size_t lds = sean_bwd_general_lds(K);
         DASR_LAUNCH((k_sean_bwd_a<T>), dim3(tiles, B, dasr_cdiv(C, 64)), dim3(256), lds, stream, g, dout, out, t, mean, var,

@@ -633,6 +633,14 @@ def sean_mod(tape, t, gb2, mask, D, bias_g, bias_b, alpha_g, alpha_b, residual, 
     if gb2.event is not None:                # gamma2/beta2 were computed on the side stream
         torch.cuda.current_stream().wait_event(gb2.event)
         gb2.data.record_stream(torch.cuda.current_stream())
+        # Resized mask planes / region bytes were allocated on the side stream too (MaskPack.resized under
+        # tape.on_stream) and are read HERE and in this node's backward.  Without the record their memory goes back to the
+        # side stream's pool the moment the last SEAN's backward closure is dropped - while that backward may still be
+        # queued - and the depth-branch backward that follows on the side stream allocates and writes into it (seen as a
+        # wrong dD of the first depth block with half-resolution soft masks).
+        for m in (mask.planes, mask.region):
+            if m is not None and m.is_cuda:
+                m.record_stream(torch.cuda.current_stream())
     mean, var = t.stats if t.stats is not None else ops.instnorm_stats(t.data)
     y = ops.sean_fwd(t.data, mean, var, gb2.data, mask.planes, mask.region, mask.flag, D.data, bias_g.data, bias_b.data,
                      alpha_g.data, alpha_b.data, residual.data if residual is not None else None, relu,
@@ -698,14 +706,9 @@ class MaskPack:
         if region is not None:               # prepared on the device (one-hot by construction) or resized from a pack
             self.region, self.flag = region, flag
             return
+        # the soft-mask kernels take as many regions as the one-hot ones (ops.soft_mask_max_regions() = 16): the flag
+        # stays on the device for every K, the host never reads it
         self.region, self.flag = ops.mask_compress(planes)
-        if planes.shape[1] > ops.soft_mask_max_regions():
-            # more regions than the soft-mask kernels hold in LDS (K = 15, 16): the device cannot fall back to them, so
-            # the flag has to be known here - the one place the host still reads it
-            if int(self.flag.item()) != 0:
-                raise NotImplementedError("dasr_amd: soft (non one-hot) masks are supported for up to %d regions, got %d"
-                                          % (ops.soft_mask_max_regions(), planes.shape[1]))
-            self.flag = None
 
     def resized(self, H, W):
         """F.interpolate(mask, mode='nearest') at a block's feature size (normalization.py:59), once per size per

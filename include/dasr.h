@@ -276,6 +276,9 @@ int dasr_dynk_bwd(const float* dD, const float* st, const float* stp, const floa
  * mask: NCHW [B,K,H,W] as the reference delivers it (any float values); bias_gamma/bias_beta [C] are the
  * mlp_gamma_s / mlp_beta_s biases; alpha_gamma / alpha_beta are 1-element DEVICE tensors (trainable, normalization.py:30-35).
  * region / onehot_flag: outputs of dasr_mask_compress for the same mask.  Both NULL: general kernel only.
+ * The general (soft-mask) kernels run the dynamic convolution as a per-sample GEMM on the exact-fp32 matrix cores
+ * (contraction over the 9*K (tap, region) pairs; backward: dD = A^T . [dgamma1 | dbeta1] over the pixels, per-workgroup
+ * slabs summed in a fixed order) when C % 4 == 0, for K up to 16; C % 4 != 0 falls back to scalar kernels, K <= 14.
  * Both given: both kernels are launched and the flag decides ON THE DEVICE which one works.  region given and
  * onehot_flag NULL: the caller has read the flag (== 0) itself and vouches for one-hot masks: gather kernel only.
  */
@@ -303,10 +306,8 @@ int dasr_sean_bwd(const float* dout, const float* out, const float* t, const flo
                   float* dt_amax, float* dgb2_amax, void* workspace, size_t workspace_bytes, int relu, int B, int H, int W,
                   int C, int K, float eps, void* stream);
 
-/* Largest K for which the soft-mask (general) kernels run forward and backward (their backward keeps two
- * [2][9][K][64] tables in LDS).  With more regions (up to 16) only one-hot masks are supported: pass region bytes with
- * onehot_flag NULL, i.e. read the flag of dasr_mask_compress yourself; otherwise dasr_sean_bwd returns
- * DASR_E_UNSUPPORTED. */
+/* Largest K for which the soft-mask (general) kernels run forward and backward: 16, the same as for one-hot masks
+ * (C % 4 == 0; the scalar fallback for other channel counts returns DASR_E_UNSUPPORTED above K = 14). */
 int dasr_sean_soft_mask_max_regions(void);
 
 /* ---- region-wise average pooling (depth matrix) ---------------------------------------------------

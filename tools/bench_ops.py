@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Per-op timing on the GPU (HIP events on the launch stream): SEAN fwd/bwd and the hot conv shapes.
-Usage: python tools/bench_ops.py [--batch 16] [--iters 10]"""
+Usage: python tools/bench_ops.py [--batch 16] [--iters 10] [--soft]
+--soft: SEAN only; adds forward and backward through the general (soft-mask) path, on the one-hot-valued masks and on a truly
+soft mask (0.7*mk + 0.3*rand: all 9*K terms of the dynamic convolution live)."""
 import argparse
 import os
 import sys
@@ -30,7 +32,11 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--only", default="")
     ap.add_argument("--amax", action="store_true", help="SEAN forward: the instantiation that also leaves max |out| behind")
+    ap.add_argument("--soft", action="store_true", help="SEAN only: the general (soft-mask) path, forward and backward, "
+                    "on one-hot-valued and on truly soft masks")
     a = ap.parse_args()
+    if a.soft:
+        a.only = "sean"
     dev = torch.device("cuda")
     B, H, W, C, K = a.batch, 128, 160, 64, 10
     torch.manual_seed(0)
@@ -63,6 +69,16 @@ def main():
         us = timeit(lambda: ops.sean_bwd(dout, out, t, mean, var, gb2, mk, region, flag, D, bg, bb, ag, ab, True, True),
                     a.iters)
         print("sean_bwd (fast)           %8.1f us  %7.1f GB/s (12C floats/px)" % (us, px * 12 * C * 4 / us / 1e3))
+        if a.soft:
+            soft = (0.7 * mk + 0.3 * torch.rand(mk.shape, device=dev)).contiguous()
+            for name, m in (("one-hot-valued", mk), ("truly soft", soft)):
+                for rname, r in (("", None), ("+res", resid)):
+                    us = timeit(lambda: ops.sean_fwd(t, mean, var, gb2, m, None, None, D, bg, bb, ag, ab, r, True), a.iters)
+                    print("sean_fwd%-4s general path, %-14s %8.1f us" % (rname, name, us))
+                o = ops.sean_fwd(t, mean, var, gb2, m, None, None, D, bg, bb, ag, ab, resid, True)
+                us = timeit(lambda: ops.sean_bwd(dout, o, t, mean, var, gb2, m, None, None, D, bg, bb, ag, ab, True, True),
+                            a.iters)
+                print("sean_bwd     general path, %-14s %8.1f us" % (name, us))
     if not a.only or "dynk" in a.only:
         L = 256
         st = torch.randn(B, K, L, device=dev)
