@@ -1242,8 +1242,33 @@ __global__ void __launch_bounds__(256, 2) k_conv3x3_wgrad_split(SplitWgradArgs a
 // and the K loop is the one of k_conv3x3_wgrad_bf16 (conv_bf16_mfma.hip) on them: operands come out of LDS as MFMA
 // fragments through ds_read_b64_tr_b16 (K = pixels: the transpose of the staged layout), the three taps of a kernel row
 // share ONE 12-pixel read per plane (dx = 0: dwords 0..3, dx = 2: dwords 1..4, dx = 1: v_alignbit of neighbours): per K-step
-// 22 transposed reads + 24 VALU + 27 MFMAs.  The bias gradient is summed from the staging registers (exact fp32 values).
+// 22 transposed reads + ~28 VALU + 27 MFMAs.  The bias gradient is summed from the staging registers (exact fp32 values).
+//
+// Tile order and the row ring.  Slab p of P sums the CONTIGUOUS tiles [p ntiles / P, (p + 1) ntiles / P) of the order (image,
+// column strip tx, ty) with ty fastest, and workgroup blockIdx.y walks the slabs [y P / gridDim.y, (y + 1) P / gridDim.y)
+// - one slab in the plain launch, a long list under impl + 2, with the same slabs and so the same result bit for bit -
+// down 32-pixel column strips.  The x planes keep their
+// TH + 2 halo rows in row SLOTS: image row gy lives in slot (gy + 1) mod (TH + 2), wherever the tile starts, and the K loop
+// reads halo row py + dy through its slot (wave-uniform arithmetic, on the scalar unit).  A tile that continues the strip
+// of its predecessor finds its top halo row and first row where the predecessor left them - its last row and bottom halo
+// row - and stages only the TH new rows into the slots of the TH oldest ones: each row of x is fetched, scaled, split and
+// written once per workgroup, not (TH + 2) / TH times (<2,2>: 3200 -> 2112 staged 16-byte pieces per tile).  A walk's first
+// tile and every first tile of a strip (new strip, new image) stage all TH + 2 rows.  Rows outside the image are zero in
+// the ring because their loads go through a descriptor of zero bytes; the last tile of a strip is always followed by a
+// full stage, so a bottom halo never serves as the next strip's top.  EVERY instantiation has the ring (4, 6 or 10 slots):
+// measured per launch at the bench shapes, <2,2> 336 -> 302 us (128 -> 128) and 101 -> 94 (64 -> 64), <1,4> 1320 -> 1232, and the
+// ring on top of the new tile order <2,1> 226 -> 210, <1,1> 394 -> 371.
+// Staging addresses: a thread's piece is (row, pixel tid / (C / 4) + k 256 / (C / 4), channel quad tid % (C / 4)) for the 32
+// pixels of a row that start at its left halo column - shifts and masks, computed once per thread - plus ONE piece of the
+// halo columns 32, 33.  Rows are addressed through a descriptor of THEIR OWN (base of the row, W C 4 bytes; zero bytes for
+// a row outside the image): the range check gives the zero padding of the left and right border and of the ragged strip
+// with no compare, and the per-tile part of an offset is one scalar.
+// Measured and dropped: the next tile's loads issued before the K loop and stored after the barrier that ends it (nine
+// more 16-byte pieces live across the loop: <2,2> then needs all 256 registers, no spill; every other instantiation
+// spills 100 - 276 bytes) - no change of the isolated launch time at either <2,2> shape: the second workgroup of the CU
+// already covers the load latency.
 __host__ __device__ constexpr int sw2_stride(int ch) { return ch == 32 ? 32 : ch + 32; }    // fp16 elements per pixel and plane
+template <int V> struct SwInt { static constexpr int value = V; };
 __device__ __forceinline__ s16x4 sp_tr16(const f16_t* p) {
     const bf16x4 r = lds_read_tr16((const bf16_t*)p);
     s16x4 v;
@@ -1257,8 +1282,9 @@ __global__ void __launch_bounds__(256, 2) k_conv3x3_wgrad_split2(SplitWgradArgs 
     constexpr int PAIRS = MT * NTW, G = 4 / PAIRS;
     constexpr int SXP = sw2_stride(CIG), SDP = sw2_stride(COG);
     constexpr int NXE = (TH + 2) * HW * SXP, NDE = TH * SW_TW * SDP;
-    f16_t* sX0 = (f16_t*)smem;                                  // [(TH+2)*HW][SXP]: fp16(x s)
-    f16_t* sX1 = sX0 + NXE;                                     //                    what that rounding left
+    constexpr int NSLOT = TH + 2;
+    f16_t* sX0 = (f16_t*)smem;                                  // [(TH+2) row slots][HW][SXP]: fp16(x s)
+    f16_t* sX1 = sX0 + NXE;                                     //                              what that rounding left
     f16_t* sD0 = sX1 + NXE;                                     // [TH*TW][SDP]
     f16_t* sD1 = sD0 + NDE;
     const int tid = threadIdx.x, lane = tid & 63, wv = DASR_UNIFORM((int)(tid >> 6));
@@ -1269,13 +1295,7 @@ __global__ void __launch_bounds__(256, 2) k_conv3x3_wgrad_split2(SplitWgradArgs 
     const int ci0 = (blockIdx.x / cgroups) * CIG, co0 = (blockIdx.x % cgroups) * COG;
     const int tiles_x = (a.W + SW_TW - 1) / SW_TW, tiles_y = (a.H + TH - 1) / TH;
 
-    f32x16 acc[9];
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
     const bool do_bias = a.bslabs != nullptr && ci0 == 0;       // (workgroup-uniform)
-    float4 bs = make_float4(0.f, 0.f, 0.f, 0.f);                // this thread's channel quad (tid % (COG / 4)) of sum dconv
     float sx, sd, inv;
     {
         __shared__ float s_red[32];
@@ -1289,7 +1309,7 @@ __global__ void __launch_bounds__(256, 2) k_conv3x3_wgrad_split2(SplitWgradArgs 
     // transposed-read lane roles: lane 4q+p of its 16-lane group passes the address of pixel row q, channels 4p..4p+3 of the
     // group's 16 channels; groups 0,1 cover channels 0..15 / 16..31 of pixels 0..7 of the K-step, groups 2,3 pixels 8..15
     const int tq = (lane & 15) >> 2, tp = lane & 3, tg = (lane >> 4) & 1;
-    const int xoff = 32 * mt + 16 * tg + 4 * tp, doff = 32 * nt + 16 * tg + 4 * tp;
+    const int xlane = (8 * lh + tq) * SXP + 32 * mt + 16 * tg + 4 * tp, dlane = (8 * lh + tq) * SDP + 32 * nt + 16 * tg + 4 * tp;
     // four values times the tensor's scale -> 4 + 4 fp16 (one 8-byte LDS write per plane)
     auto put = [&](f16_t* p0, f16_t* p1, int off, float4 v, float s) {
         const float f[4] = {v.x * s, v.y * s, v.z * s, v.w * s};
@@ -1302,139 +1322,194 @@ __global__ void __launch_bounds__(256, 2) k_conv3x3_wgrad_split2(SplitWgradArgs 
         __builtin_memcpy(p0 + off, h0, 8);
         __builtin_memcpy(p1 + off, h1, 8);
     };
+    // staging roles (tile-independent): KX (KD) pieces per thread and row of x (dconv), PXS (PDS) pixels apart, and the
+    // thread's piece of the halo columns 32, 33 of row er of a batch of rows
+    constexpr int C4 = CIG / 4, D4 = COG / 4;
+    constexpr int KX = SW_TW * C4 / 256, PXS = 256 / C4, KD = SW_TW * D4 / 256, PDS = 256 / D4;
+    static_assert(KX * 256 == SW_TW * C4 && KD * 256 == SW_TW * D4, "a row of pieces is a whole number of passes of the workgroup");
+    const int xc4 = tid % C4, xpx = tid / C4, dc4 = tid % D4, dpx = tid / D4;
+    const int gxo = ((xpx - 1) * a.Cin + ci0 + 4 * xc4) * (int)sizeof(float);      // (negative for halo column 0 of strip 0: out of range)
+    const int gdo = (dpx * a.Cout + co0 + 4 * dc4) * (int)sizeof(float);
+    const int lxo = xpx * SXP + 4 * xc4, ldo = dpx * SDP + 4 * dc4;
+    const int er = tid / (2 * C4), epx = SW_TW + (xpx & 1);
+    const unsigned xrow_bytes = (unsigned)a.W * a.Cin * sizeof(float), drow_bytes = (unsigned)a.W * a.Cout * sizeof(float);
 
-    for (int tile = blockIdx.y; tile < a.ntiles; tile += a.P) {
-        const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, b = tile / (tiles_x * tiles_y);
-        const int x0 = tx * SW_TW, y0 = ty * TH;
-        // stage the tile: every global load of a thread before the first LDS write (see k_conv3x3_wgrad_mfma)
-        constexpr int NX = (TH + 2) * HW * (CIG / 4), NXI = (NX + 255) / 256;        // 64 x 64 block: 2176 float4 pieces, 9 per thread
-        constexpr int ND = TH * SW_TW * (COG / 4), NDI = (ND + 255) / 256;           //                1024: 4 per thread
-        // (144 accumulator registers are resident: the x pieces go in two batches, the second one after the barrier)
-        constexpr int XA = NDI >= 8 ? 1 : (8 - NDI < NXI ? 8 - NDI : NXI);
-        float4 vx[NXI - XA > XA ? NXI - XA : XA], vd[NDI];
-        // (buffer loads: a 32-bit offset per piece, the zero padding from the descriptor's range check - SQ counters of the
-        // first form, with 64-bit predicated loads: 6.9 VALU per MFMA, most of them this staging pass)
-        const BufRsrc rx = dasr_make_rsrc(a.x + (size_t)b * a.H * a.W * a.Cin, (size_t)a.H * a.W * a.Cin * sizeof(float));
-        const BufRsrc rd = dasr_make_rsrc(a.dy + (size_t)b * a.H * a.W * a.Cout, (size_t)a.H * a.W * a.Cout * sizeof(float));
-        auto ldx = [&](int u) {
-            const int idx = tid + 256 * u;
-            const int c4 = idx % (CIG / 4), pix = idx / (CIG / 4);
-            const int gy = y0 + pix / HW - 1, gx = x0 + pix % HW - 1;
-            const bool ok = idx < NX && (unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W;
-            const u32x4_t r = dasr_buffer_load16(rx, ok ? (unsigned)(((gy * a.W + gx) * a.Cin + ci0 + 4 * c4) * (int)sizeof(float)) : DASR_OOB);
-            float4 v;
-            __builtin_memcpy(&v, &r, 16);
-            return v;
-        };
-        auto stx = [&](int u, float4 v) {
-            const int idx = tid + 256 * u;
-            if (idx < NX) put(sX0, sX1, (idx / (CIG / 4)) * SXP + 4 * (idx % (CIG / 4)), v, sx);
-        };
+    // slab p sums the tiles [p ntiles / P, (p + 1) ntiles / P); this workgroup walks the slabs [p0, p1) - one of them
+    // (gridDim.y = P), or a long list under impl + 2 (tests) - without a break in the tile order or in the ring
+    const int p0 = (int)((long long)blockIdx.y * a.P / gridDim.y), p1 = (int)((long long)(blockIdx.y + 1) * a.P / gridDim.y);
+    int tile = (int)((long long)p0 * a.ntiles / a.P);
+    int ty = tile % tiles_y, tx = (tile / tiles_y) % tiles_x, b = tile / (tiles_y * tiles_x);
+    bool full = true;                           // stage all TH + 2 rows: at the head of the walk and of every strip
+    // (buffer loads: a 32-bit offset per piece, the zero padding from the descriptor's range check - SQ counters of the
+    // first form, with 64-bit predicated loads: 6.9 VALU per MFMA, most of them this staging pass)
+    // halo rows [R0, R0 + N) of x of the tile at (b_, x0, y0): N KX row pieces and the halo-column piece per thread
+    auto ldx = [&](auto R0, auto N, float4* v, int b_, int x0, int y0) {
+        constexpr int r0 = decltype(R0)::value, n = decltype(N)::value;
+        const float* ximg = a.x + (size_t)b_ * a.H * a.W * a.Cin;
+        const BufRsrc rimg = dasr_make_rsrc(ximg, (size_t)a.H * a.W * a.Cin * sizeof(float));
 #pragma unroll
-        for (int u = 0; u < XA; ++u) vx[u] = ldx(u);
+        for (int j = 0; j < n; ++j) {
+            const int gy = y0 - 1 + r0 + j;
+            const bool in = (unsigned)gy < (unsigned)a.H;
+            const BufRsrc rr = dasr_make_rsrc(ximg + (size_t)(in ? gy : 0) * a.W * a.Cin, in ? xrow_bytes : 0u);
 #pragma unroll
-        for (int u = 0; u < NDI; ++u) {
-            const int idx = tid + 256 * u;
-            const int c4 = idx % (COG / 4), pix = idx / (COG / 4);
-            const int gy = y0 + pix / SW_TW, gx = x0 + pix % SW_TW;
-            const bool ok = idx < ND && gy < a.H && gx < a.W;
-            const u32x4_t r = dasr_buffer_load16(rd, ok ? (unsigned)(((gy * a.W + gx) * a.Cout + co0 + 4 * c4) * (int)sizeof(float)) : DASR_OOB);
-            __builtin_memcpy(&vd[u], &r, 16);
+            for (int k = 0; k < KX; ++k) {
+                const u32x4_t q = dasr_buffer_load16(rr, (unsigned)(gxo + (x0 + k * PXS) * a.Cin * (int)sizeof(float)));
+                __builtin_memcpy(&v[j * KX + k], &q, 16);
+            }
         }
-        __syncthreads();                        // every wave is done with the previous tile
+        const int gy = y0 - 1 + r0 + er, gx = x0 - 1 + epx;
+        const bool ok = er < n && (unsigned)gy < (unsigned)a.H && gx < a.W;
+        const u32x4_t q = dasr_buffer_load16(rimg, ok ? (unsigned)(((gy * a.W + gx) * a.Cin + ci0 + 4 * xc4) * (int)sizeof(float)) : DASR_OOB);
+        __builtin_memcpy(&v[n * KX], &q, 16);
+    };
+    auto stx = [&](auto R0, auto N, const float4* v, int slot0) {
+        constexpr int r0 = decltype(R0)::value, n = decltype(N)::value;
+        auto slot_of = [&](int r) { const int s = slot0 + r; return s >= NSLOT ? s - NSLOT : s; };
 #pragma unroll
-        for (int u = 0; u < XA; ++u) stx(u, vx[u]);
+        for (int j = 0; j < n; ++j) {
+            const int o = slot_of(r0 + j) * (HW * SXP) + lxo;
 #pragma unroll
-        for (int u = 0; u < NDI; ++u) {
-            const int idx = tid + 256 * u;
-            if (idx < ND) put(sD0, sD1, (idx / (COG / 4)) * SDP + 4 * (idx % (COG / 4)), vd[u], sd);
-            if (do_bias) { bs.x += vd[u].x; bs.y += vd[u].y; bs.z += vd[u].z; bs.w += vd[u].w; }   // (zeros outside the image)
+            for (int k = 0; k < KX; ++k) put(sX0, sX1, o + k * PXS * SXP, v[j * KX + k], sx);
         }
+        if (er < n) put(sX0, sX1, slot_of(r0 + er) * (HW * SXP) + epx * SXP + 4 * xc4, v[n * KX], sx);
+    };
+    // (144 accumulator registers are resident: the TH rows a ring step needs and dconv are one batch of loads, the two rows a
+    // full stage adds a second one after the barrier)
+    float4 vx[TH * KX + 1], vd[TH * KD];
+    auto load_a = [&](int b_, int tx_, int ty_) {
+        const int x0 = tx_ * SW_TW, y0 = ty_ * TH;
+        ldx(SwInt<2>(), SwInt<TH>(), vx, b_, x0, y0);
+        const float* dimg = a.dy + (size_t)b_ * a.H * a.W * a.Cout;
 #pragma unroll
-        for (int u = XA; u < NXI; ++u) vx[u - XA] = ldx(u);
+        for (int r = 0; r < TH; ++r) {
+            const bool in = y0 + r < a.H;
+            const BufRsrc rr = dasr_make_rsrc(dimg + (size_t)(in ? y0 + r : 0) * a.W * a.Cout, in ? drow_bytes : 0u);
 #pragma unroll
-        for (int u = XA; u < NXI; ++u) stx(u, vx[u - XA]);
-        __syncthreads();
-        // K-step s = 16 consecutive pixels of one tile row.  EXEC is all ones here (the tile loop and the K-step split are
-        // wave-uniform), as ds_read_b64_tr_b16 requires.
-        constexpr int NS = TH * (SW_TW / 16);
+            for (int k = 0; k < KD; ++k) {
+                const u32x4_t q = dasr_buffer_load16(rr, (unsigned)(gdo + (x0 + k * PDS) * a.Cout * (int)sizeof(float)));
+                __builtin_memcpy(&vd[r * KD + k], &q, 16);
+            }
+        }
+    };
+    for (int p = p0; p < p1; ++p) {
+        const int t1 = (int)((long long)(p + 1) * a.ntiles / a.P);
+        f32x16 acc[9];
+#pragma unroll
+        for (int t = 0; t < 9; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+        float4 bs = make_float4(0.f, 0.f, 0.f, 0.f);                // this thread's channel quad (tid % (COG / 4)) of sum dconv
+        for (; tile < t1; ++tile) {
+            const int slot0 = (ty * TH) % NSLOT;                    // slot of halo row 0 of this tile (image row y0 - 1)
+            auto slot_of = [&](int r) { const int s = slot0 + r; return s >= NSLOT ? s - NSLOT : s; };
+            load_a(b, tx, ty);
+            __syncthreads();                        // every wave is done with the previous tile
+            stx(SwInt<2>(), SwInt<TH>(), vx, slot0);
+#pragma unroll
+            for (int u = 0; u < TH * KD; ++u) {
+                put(sD0, sD1, (u / KD) * (SW_TW * SDP) + (u % KD) * (PDS * SDP) + ldo, vd[u], sd);
+                if (do_bias) { bs.x += vd[u].x; bs.y += vd[u].y; bs.z += vd[u].z; bs.w += vd[u].w; }   // (zeros outside the image)
+            }
+            if (full) {
+                ldx(SwInt<0>(), SwInt<2>(), vx, b, tx * SW_TW, ty * TH);
+                stx(SwInt<0>(), SwInt<2>(), vx, slot0);
+            }
+            // the next tile of the order: down the strip, then the next strip, then the next image
+            full = false;
+            if (++ty == tiles_y) {
+                ty = 0;
+                full = true;
+                if (++tx == tiles_x) { tx = 0; ++b; }
+            }
+            __syncthreads();
+            // K-step s = 16 consecutive pixels of one tile row.  EXEC is all ones here (the tile loop and the K-step split are
+            // wave-uniform), as ds_read_b64_tr_b16 requires.
+            constexpr int NS = TH * (SW_TW / 16);
 #pragma unroll 1
-        for (int s = grp; s < NS; s += G) {
-            const int py = s / (SW_TW / 16), px0 = 16 * (s % (SW_TW / 16)) + 8 * lh + tq;
-            f16x8 Bd[2];
-            {
-                const int o = (py * SW_TW + px0) * SDP + doff;
-                const s16x4 l0 = sp_tr16(sD0 + o), u0 = sp_tr16(sD0 + o + 4 * SDP);
-                const s16x4 l1 = sp_tr16(sD1 + o), u1 = sp_tr16(sD1 + o + 4 * SDP);
-                __builtin_memcpy(&Bd[0], &l0, 8); __builtin_memcpy((char*)&Bd[0] + 8, &u0, 8);
-                __builtin_memcpy(&Bd[1], &l1, 8); __builtin_memcpy((char*)&Bd[1] + 8, &u1, 8);
-            }
-            const int xo = (py * HW + px0) * SXP + xoff;
-            // (pixels 10, 11 of the last window of a tile row belong to the next row / lie past the tile: read, unused)
-#pragma unroll
-            for (int dy = 0; dy < 3; ++dy) {
-                f16x8 A[3][2];                                  // [dx][plane]
-#pragma unroll
-                for (int pl = 0; pl < 2; ++pl) {
-                    const f16_t* ap = (pl == 0 ? sX0 : sX1) + xo + dy * HW * SXP;
-                    const s16x4 a0 = sp_tr16(ap), a1 = sp_tr16(ap + 4 * SXP), a2 = sp_tr16(ap + 8 * SXP);
-                    unsigned R[6];
-                    __builtin_memcpy(&R[0], &a0, 8);
-                    __builtin_memcpy(&R[2], &a1, 8);
-                    __builtin_memcpy(&R[4], &a2, 8);
-                    const unsigned V0[4] = {R[0], R[1], R[2], R[3]}, V2[4] = {R[1], R[2], R[3], R[4]};
-                    unsigned V1[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) V1[e] = (R[e] >> 16) | (R[e + 1] << 16);
-                    __builtin_memcpy(&A[0][pl], V0, 16);
-                    __builtin_memcpy(&A[1][pl], V1, 16);
-                    __builtin_memcpy(&A[2][pl], V2, 16);
+            for (int s = grp; s < NS; s += G) {
+                const int py = s / (SW_TW / 16), pu = 16 * (s % (SW_TW / 16));       // (wave-uniform)
+                f16x8 Bd[2];
+                {
+                    const int o = (py * SW_TW + pu) * SDP + dlane;
+                    const s16x4 l0 = sp_tr16(sD0 + o), u0 = sp_tr16(sD0 + o + 4 * SDP);
+                    const s16x4 l1 = sp_tr16(sD1 + o), u1 = sp_tr16(sD1 + o + 4 * SDP);
+                    __builtin_memcpy(&Bd[0], &l0, 8); __builtin_memcpy((char*)&Bd[0] + 8, &u0, 8);
+                    __builtin_memcpy(&Bd[1], &l1, 8); __builtin_memcpy((char*)&Bd[1] + 8, &u1, 8);
                 }
+                // (pixels 10, 11 of the last window of a tile row belong to the next slot / lie past the planes: read, unused)
 #pragma unroll
-                for (int dx = 0; dx < 3; ++dx) acc[3 * dy + dx] = SpFrag<2>::mma(A[dx], Bd, acc[3 * dy + dx]);
-            }
-        }
-    }
-    float* sR = (float*)smem;
-    if (G > 1) {
-        // waves grp = 1 .. G-1 hand their accumulators to wave grp = 0 of the same pair, one tap at a time through
-        // (G - 1) * PAIRS * 4 KB of the (now idle) staging LDS
+                for (int dy = 0; dy < 3; ++dy) {
+                    const int xo = (slot_of(py + dy) * HW + pu) * SXP + xlane;
+                    f16x8 A[3][2];                                  // [dx][plane]
 #pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            __syncthreads();
-            if (grp > 0) {
-                float* q = sR + ((grp - 1) * PAIRS + pair) * 1024 + lane;
+                    for (int pl = 0; pl < 2; ++pl) {
+                        const f16_t* ap = (pl == 0 ? sX0 : sX1) + xo;
+                        const s16x4 a0 = sp_tr16(ap), a1 = sp_tr16(ap + 4 * SXP), a2 = sp_tr16(ap + 8 * SXP);
+                        unsigned R[6];
+                        __builtin_memcpy(&R[0], &a0, 8);
+                        __builtin_memcpy(&R[2], &a1, 8);
+                        __builtin_memcpy(&R[4], &a2, 8);
+                        const unsigned V0[4] = {R[0], R[1], R[2], R[3]}, V2[4] = {R[1], R[2], R[3], R[4]};
+                        unsigned V1[4];
 #pragma unroll
-                for (int r = 0; r < 16; ++r) q[64 * r] = acc[t][r];
-            }
-            __syncthreads();
-            if (grp == 0) {
-                for (int gg = 0; gg < G - 1; ++gg) {
-                    const float* q = sR + (gg * PAIRS + pair) * 1024 + lane;
+                        for (int e = 0; e < 4; ++e) V1[e] = (R[e] >> 16) | (R[e + 1] << 16);
+                        __builtin_memcpy(&A[0][pl], V0, 16);
+                        __builtin_memcpy(&A[1][pl], V1, 16);
+                        __builtin_memcpy(&A[2][pl], V2, 16);
+                    }
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[t][r] += q[64 * r];
+                    for (int dx = 0; dx < 3; ++dx) acc[3 * dy + dx] = SpFrag<2>::mma(A[dx], Bd, acc[3 * dy + dx]);
                 }
             }
         }
-    }
-    if (do_bias) {                              // the threads' channel-quad sums meet through LDS: threads q, q + COG/4, ... own quad q
-        __syncthreads();
-        *(float4*)(sR + 4 * tid) = bs;
-        __syncthreads();
-        if (tid < COG) {
-            float r = 0.f;
-            for (int t = tid >> 2; t < 256; t += COG / 4) r += sR[4 * t + (tid & 3)];
-            a.bslabs[(size_t)blockIdx.y * a.Cout + co0 + tid] = r;
+        float* sR = (float*)sD0;                    // (the dconv planes: restaged by every tile; the x ring stays as it is)
+        static_assert(4 * NDE >= (G - 1) * PAIRS * 4096 && 4 * NDE >= 4096, "the exchanges below fit the dconv planes");
+        if (G > 1) {
+            // waves grp = 1 .. G-1 hand their accumulators to wave grp = 0 of the same pair, one tap at a time through
+            // (G - 1) * PAIRS * 4 KB of the (now idle) dconv planes
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+                __syncthreads();
+                if (grp > 0) {
+                    float* q = sR + ((grp - 1) * PAIRS + pair) * 1024 + lane;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) q[64 * r] = acc[t][r];
+                }
+                __syncthreads();
+                if (grp == 0) {
+                    for (int gg = 0; gg < G - 1; ++gg) {
+                        const float* q = sR + (gg * PAIRS + pair) * 1024 + lane;
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) acc[t][r] += q[64 * r];
+                    }
+                }
+            }
         }
-    }
-    float* slab = a.slabs + (size_t)blockIdx.y * 9 * a.Cin * a.Cout;
-    if (grp != 0) return;
+        if (do_bias) {                              // the threads' channel-quad sums meet through LDS: threads q, q + COG/4, ... own quad q
+            __syncthreads();
+            *(float4*)(sR + 4 * tid) = bs;
+            __syncthreads();
+            if (tid < COG) {
+                float r = 0.f;
+                for (int t = tid >> 2; t < 256; t += COG / 4) r += sR[4 * t + (tid & 3)];
+                a.bslabs[(size_t)p * a.Cout + co0 + tid] = r;
+            }
+        }
+        float* slab = a.slabs + (size_t)p * 9 * a.Cin * a.Cout;
+        if (grp == 0) {
+            // (opaque copies: the 144 store addresses are computed here, where the staging registers are free - hoisted out
+            // of the slab loop as loop invariants they would live across the K loop, 1 KB of scratch per lane)
+            int cin_ = a.Cin, cout_ = a.Cout, lo = (ci0 + 32 * mt + 4 * lh) * a.Cout + co0 + 32 * nt + li;
+#ifndef DASR_HIPEMU
+            asm volatile("" : "+s"(cin_), "+s"(cout_), "+v"(lo));
+#endif
 #pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
+            for (int tap = 0; tap < 9; ++tap) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int ci = ci0 + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            slab[((size_t)tap * a.Cin + ci) * a.Cout + co0 + 32 * nt + li] = acc[tap][r] * inv;
+                for (int r = 0; r < 16; ++r)
+                    slab[((size_t)tap * cin_ + (r & 3) + 8 * (r >> 2)) * cout_ + lo] = acc[tap][r] * inv;
+            }
         }
     }
 }
@@ -1470,7 +1545,6 @@ static int sw_launch(const float* x, const float* xmax, const float* dconv, cons
     float* bslabs = dbias ? slabs + (size_t)P * nW : nullptr;
     SplitWgradArgs a{xmax, dmax, x, dconv, slabs, bslabs, B, H, W, Cin, Cout, P, ntiles};
     const int th = sw_th(MT, NTW);
-    const dim3 grid(groups, P);
     // fp16 x 2: the staged-split kernel (128 -> 128 424 -> 317 us, 64 -> 64 134 -> 107, 32 -> 128 at 512 x 640 1716 -> 1349, 32 -> 32
     // there 544 -> 435, 64 -> 32 277 -> 265; before its staging went through buffer descriptors the small blocks lost with it).
     // impl + 64 (A/B, tests): the first version - fp32 tiles, operands split per K-step.
@@ -1479,6 +1553,9 @@ static int sw_launch(const float* x, const float* xmax, const float* dconv, cons
     if (NP == 2 && (impl & 64) == 0 && fits32) {
         size_t lds2 = sizeof(f16_t) * 2 * (size_t)((th + 2) * (SW_TW + 2) * sw2_stride(32 * MT) + th * SW_TW * sw2_stride(32 * NTW));
         if (lds2 < 4 * 4096) lds2 = 4 * 4096;                     // (the bias-gradient exchange: 256 float4)
+        // impl + 2 (tests): at most three workgroups per channel block, each walking a long list of slabs (strip and image
+        // changes inside a walk at small shapes); the slabs, and with them the result, are those of the plain launch
+        const dim3 grid(groups, (impl & 2) && P > 3 ? 3 : P);
         if (MT == 2 && NTW == 2)      DASR_LAUNCH((k_conv3x3_wgrad_split2<2, 2>), grid, dim3(256), lds2, stream, a);
         else if (MT == 1 && NTW == 4) DASR_LAUNCH((k_conv3x3_wgrad_split2<1, 4>), grid, dim3(256), lds2, stream, a);
         else if (MT == 2 && NTW == 1) DASR_LAUNCH((k_conv3x3_wgrad_split2<2, 1>), grid, dim3(256), lds2, stream, a);
@@ -1487,6 +1564,7 @@ static int sw_launch(const float* x, const float* xmax, const float* dconv, cons
         return wgrad_reduce_launch(slabs, dw, nW, P, stream, bslabs, dbias, Cout);
     }
     const size_t lds = sizeof(float) * (size_t)((th + 2) * (SW_TW + 2) * 32 * MT + th * SW_TW * 32 * NTW);
+    const dim3 grid(groups, P);
     if (MT == 2 && NTW == 2)      DASR_LAUNCH((k_conv3x3_wgrad_split<2, 2, NP>), grid, dim3(256), lds, stream, a);
     else if (MT == 1 && NTW == 4) DASR_LAUNCH((k_conv3x3_wgrad_split<1, 4, NP>), grid, dim3(256), lds, stream, a);
     else if (MT == 2 && NTW == 1) DASR_LAUNCH((k_conv3x3_wgrad_split<2, 1, NP>), grid, dim3(256), lds, stream, a);
