@@ -5,6 +5,14 @@
 // region[y/s][x/s]), so one pass yields all K numerators, the K areas and sum|sr-hr|; the division, the softmax
 // weighting and the trainable weights stay in PyTorch (harness.py).  HBM-bound: 24 B per HR pixel forward,
 // 36 B backward.  sr / hr are the API's NCHW tensors.
+//
+// Soft masks (any float values; the second half of this file): the mask sits INSIDE the smooth-L1,
+// num_k = sum smooth_l1(M_k * (sr-hr)), so a pixel contributes to every region.  One thread takes one LR-pixel-wide run
+// of s HR pixels in ALL C channels: it loads the run's K mask values once and keeps the K numerators (and the K areas,
+// summed at LR: rows with Y % s == 0 only) in registers - the kernels are instantiated per K so that every per-k loop is
+// unrolled.  8 B per HR element forward, 12 B backward, plus the LR planes; ~7 K VALU per element.
+#include <stdint.h>
+
 #include "dasr_common.h"
 
 #define LOSS_MAXK 16
@@ -86,5 +94,179 @@ extern "C" int dasr_loss_bwd(const float* sr, const float* hr, const unsigned ch
     if (K > LOSS_MAXK) return DASR_E_UNSUPPORTED;
     size_t n = (size_t)B * C * h * scale * w * scale;
     DASR_LAUNCH(k_loss_bwd, dim3(dasr_ew_grid(n)), dim3(256), 0, stream, sr, hr, region, dsums, dsr, B, C, h, w, scale, K);
+    DASR_RETURN_LAUNCH_STATUS();
+}
+
+// ---- soft masks ------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float loss_sign(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
+
+template <int K>
+__device__ __forceinline__ void loss_soft_px(float d, const float (&m)[K], float (&num)[K], float& l1) {
+    l1 += fabsf(d);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const float u = m[k] * d, au = fabsf(u);
+        num[k] += au < 1.f ? 0.5f * u * u : au - 0.5f;        // SmoothL1Loss(beta = 1) of the MASKED difference
+    }
+}
+
+template <int K>
+__device__ __forceinline__ float loss_soft_px_bwd(float d, float dl1, const float (&m)[K], const float (&coef)[K]) {
+    float g = dl1 * loss_sign(d);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const float u = m[k] * d;
+        g += coef[k] * (fabsf(u) < 1.f ? u : (u > 0.f ? 1.f : -1.f));
+    }
+    return g;
+}
+
+// run r of B*H*w -> (b, Y, lx); the K mask values of its LR pixel; offset of its first HR pixel in channel 0
+template <int K>
+__device__ __forceinline__ size_t loss_soft_run(size_t r, const float* __restrict__ mask, int C, int h, int w, int s,
+                                                float (&m)[K], bool& first_row) {
+    const int H = h * s;
+    const int lx = (int)(r % w);
+    const int Y = (int)((r / w) % H);
+    const size_t b = r / ((size_t)w * H);
+    const int y = Y / s;
+    first_row = Y == y * s;
+    const float* pm = mask + ((b * K) * h + y) * w + lx;
+#pragma unroll
+    for (int k = 0; k < K; ++k) m[k] = pm[(size_t)k * h * w];
+    return ((b * C) * H + Y) * ((size_t)w * s) + (size_t)lx * s;
+}
+
+// VEC: s % 4 == 0 and 16-byte aligned tensors, so every run starts on a 16-byte boundary (W = w * s)
+template <int K, bool VEC>
+__global__ void __launch_bounds__(256) k_loss_sums_soft(const float* __restrict__ sr, const float* __restrict__ hr,
+                                                        const float* __restrict__ mask, float* __restrict__ sums, int B,
+                                                        int C, int h, int w, int s) {
+    __shared__ float red[2 * LOSS_MAXK + 1];
+    for (int i = threadIdx.x; i < 2 * K + 1; i += 256) red[i] = 0.f;
+    __syncthreads();
+    const size_t plane = (size_t)h * s * w * s;
+    const size_t nruns = (size_t)B * h * s * w;
+    float num[K], area[K], m[K], l1 = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) num[k] = area[k] = 0.f;
+    for (size_t r = (size_t)blockIdx.x * 256 + threadIdx.x; r < nruns; r += (size_t)gridDim.x * 256) {
+        bool first_row;
+        const size_t off = loss_soft_run<K>(r, mask, C, h, w, s, m, first_row);
+        if (first_row) {                                       // the areas are sums at LR: once per LR pixel
+#pragma unroll
+            for (int k = 0; k < K; ++k) area[k] += m[k];
+        }
+        for (int c = 0; c < C; ++c) {
+            const float* ps = sr + off + c * plane;
+            const float* ph = hr + off + c * plane;
+            if (VEC) {
+                for (int j = 0; j < s; j += 4) {
+                    const f32x4 d = *reinterpret_cast<const f32x4*>(ps + j) - *reinterpret_cast<const f32x4*>(ph + j);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) loss_soft_px<K>(d[i], m, num, l1);
+                }
+            } else {
+                for (int j = 0; j < s; ++j) loss_soft_px<K>(ps[j] - ph[j], m, num, l1);
+            }
+        }
+    }
+    // wave reduction, then ONE LDS atomic per wave and sum, then one global atomic per workgroup and sum
+    const float area_scale = (float)C * (float)s * (float)s;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        float a = num[k], b = area[k];
+        for (int off = 32; off > 0; off >>= 1) {
+            a += __shfl_down(a, off, 64);
+            b += __shfl_down(b, off, 64);
+        }
+        if ((threadIdx.x & 63) == 0) {
+            atomicAdd(&red[k], a);
+            atomicAdd(&red[K + k], b * area_scale);
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) l1 += __shfl_down(l1, off, 64);
+    if ((threadIdx.x & 63) == 0) atomicAdd(&red[2 * K], l1);
+    __syncthreads();
+    for (int i = threadIdx.x; i < 2 * K + 1; i += 256) atomicAdd(&sums[i], red[i]);
+}
+
+// dsr = dsums[2K] * sign(d) + sum_k dsums[k] * M_k * smooth_l1'(M_k * d)
+template <int K, bool VEC>
+__global__ void __launch_bounds__(256) k_loss_bwd_soft(const float* __restrict__ sr, const float* __restrict__ hr,
+                                                       const float* __restrict__ mask, const float* __restrict__ dsums,
+                                                       float* __restrict__ dsr, int B, int C, int h, int w, int s) {
+    const size_t plane = (size_t)h * s * w * s;
+    const size_t nruns = (size_t)B * h * s * w;
+    float dnum[K], m[K], coef[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) dnum[k] = dsums[k];
+    const float dl1 = dsums[2 * K];
+    for (size_t r = (size_t)blockIdx.x * 256 + threadIdx.x; r < nruns; r += (size_t)gridDim.x * 256) {
+        bool first_row;
+        const size_t off = loss_soft_run<K>(r, mask, C, h, w, s, m, first_row);
+#pragma unroll
+        for (int k = 0; k < K; ++k) coef[k] = dnum[k] * m[k];
+        for (int c = 0; c < C; ++c) {
+            const float* ps = sr + off + c * plane;
+            const float* ph = hr + off + c * plane;
+            float* pd = dsr + off + c * plane;
+            if (VEC) {
+                for (int j = 0; j < s; j += 4) {
+                    const f32x4 d = *reinterpret_cast<const f32x4*>(ps + j) - *reinterpret_cast<const f32x4*>(ph + j);
+                    f32x4 g;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) g[i] = loss_soft_px_bwd<K>(d[i], dl1, m, coef);
+                    *reinterpret_cast<f32x4*>(pd + j) = g;
+                }
+            } else {
+                for (int j = 0; j < s; ++j) pd[j] = loss_soft_px_bwd<K>(ps[j] - ph[j], dl1, m, coef);
+            }
+        }
+    }
+}
+
+static inline bool loss_aligned16(const void* a, const void* b, const void* c = nullptr) {
+    return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
+}
+
+// one instantiation per K (1 .. LOSS_MAXK) and load width
+#define LOSS_SOFT_CASE(KK, KERNEL, ...)                                                                  \
+    case KK:                                                                                             \
+        if (vec) DASR_LAUNCH((KERNEL<KK, true>), dim3(dasr_ew_grid(nruns)), dim3(256), 0, stream, __VA_ARGS__);  \
+        else DASR_LAUNCH((KERNEL<KK, false>), dim3(dasr_ew_grid(nruns)), dim3(256), 0, stream, __VA_ARGS__);     \
+        break;
+#define LOSS_SOFT_DISPATCH(KERNEL, ...)                                                                          \
+    switch (K) {                                                                                                 \
+        LOSS_SOFT_CASE(1, KERNEL, __VA_ARGS__) LOSS_SOFT_CASE(2, KERNEL, __VA_ARGS__) LOSS_SOFT_CASE(3, KERNEL, __VA_ARGS__)    \
+        LOSS_SOFT_CASE(4, KERNEL, __VA_ARGS__) LOSS_SOFT_CASE(5, KERNEL, __VA_ARGS__) LOSS_SOFT_CASE(6, KERNEL, __VA_ARGS__)    \
+        LOSS_SOFT_CASE(7, KERNEL, __VA_ARGS__) LOSS_SOFT_CASE(8, KERNEL, __VA_ARGS__) LOSS_SOFT_CASE(9, KERNEL, __VA_ARGS__)    \
+        LOSS_SOFT_CASE(10, KERNEL, __VA_ARGS__) LOSS_SOFT_CASE(11, KERNEL, __VA_ARGS__) LOSS_SOFT_CASE(12, KERNEL, __VA_ARGS__) \
+        LOSS_SOFT_CASE(13, KERNEL, __VA_ARGS__) LOSS_SOFT_CASE(14, KERNEL, __VA_ARGS__) LOSS_SOFT_CASE(15, KERNEL, __VA_ARGS__) \
+        LOSS_SOFT_CASE(16, KERNEL, __VA_ARGS__)                                                                  \
+        default: return DASR_E_UNSUPPORTED;                                                                      \
+    }
+
+extern "C" int dasr_loss_sums_soft(const float* sr, const float* hr, const float* mask, float* sums, int B, int C, int h,
+                                   int w, int scale, int K, void* stream) {
+    DASR_CHECK_PTR(sr); DASR_CHECK_PTR(hr); DASR_CHECK_PTR(mask); DASR_CHECK_PTR(sums);
+    DASR_CHECK_SHAPE(B > 0 && C > 0 && h > 0 && w > 0 && scale > 0 && K > 0);
+    if (K > LOSS_MAXK) return DASR_E_UNSUPPORTED;
+    hipError_t e = hipMemsetAsync(sums, 0, sizeof(float) * (2 * K + 1), (hipStream_t)stream);
+    if (e != hipSuccess) return (int)e;
+    const size_t nruns = (size_t)B * h * scale * w;
+    const bool vec = scale % 4 == 0 && loss_aligned16(sr, hr);
+    LOSS_SOFT_DISPATCH(k_loss_sums_soft, sr, hr, mask, sums, B, C, h, w, scale)
+    DASR_RETURN_LAUNCH_STATUS();
+}
+
+extern "C" int dasr_loss_bwd_soft(const float* sr, const float* hr, const float* mask, const float* dsums, float* dsr,
+                                  int B, int C, int h, int w, int scale, int K, void* stream) {
+    DASR_CHECK_PTR(sr); DASR_CHECK_PTR(hr); DASR_CHECK_PTR(mask); DASR_CHECK_PTR(dsums); DASR_CHECK_PTR(dsr);
+    DASR_CHECK_SHAPE(B > 0 && C > 0 && h > 0 && w > 0 && scale > 0 && K > 0);
+    if (K > LOSS_MAXK) return DASR_E_UNSUPPORTED;
+    const size_t nruns = (size_t)B * h * scale * w;
+    const bool vec = scale % 4 == 0 && loss_aligned16(sr, hr, dsr);
+    LOSS_SOFT_DISPATCH(k_loss_bwd_soft, sr, hr, mask, dsums, dsr, B, C, h, w, scale)
     DASR_RETURN_LAUNCH_STATUS();
 }

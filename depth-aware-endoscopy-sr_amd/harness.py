@@ -6,7 +6,8 @@ L1 pixel loss (weight 1) + dynamic depth-aware smooth-L1 loss (weight 10, 10 tra
 weights, codes/models/modules/mask_loss.py:44-90), Adam(lr 1e-3, betas (0.9, 0.99), wd 0) over the
 generator's parameters plus the loss weights, CosineAnnealingLR_Restart stepped BEFORE the optimiser
 (codes/models/lr_scheduler.py:34-62).  Losses and optimiser stay PyTorch (north_star); the generator
-forward/backward is the HIP path.
+forward/backward is the HIP path, and so are the sums both losses need (``fused_losses``: one pass over sr / hr for one-hot
+masks and for soft masks alike; the division, the softmax weighting and the collective stay in PyTorch).
 
 Data parallel: one process per GPU (torchrun), ``torch.distributed`` backend ``nccl`` (= RCCL over
 xGMI) on the GPU box, ``gloo`` in CPU tests.  The net itself is communication-free (instance norm is
@@ -44,7 +45,7 @@ def _world(group=None):
 
 class _RegionSums(torch.autograd.Function):
     """sums = (K smooth-L1 numerators | K areas | sum|sr-hr|) in ONE pass over sr, hr (dasr_loss_sums); the
-    backward is one elementwise pass (dasr_loss_bwd).  One-hot masks only (region bytes from dasr_mask_compress)."""
+    backward is one elementwise pass (dasr_loss_bwd).  One-hot masks (region bytes from dasr_mask_compress)."""
 
     @staticmethod
     def forward(ctx, sr, hr, region, K):
@@ -61,9 +62,31 @@ class _RegionSums(torch.autograd.Function):
         return ops.loss_bwd(sr, hr, region, dsums.contiguous(), ctx.K), None, None, None
 
 
+class _RegionSumsSoft(torch.autograd.Function):
+    """The same sums for arbitrary float masks [B,K,h,w] (dasr_loss_sums_soft / dasr_loss_bwd_soft): the mask sits inside
+    the smooth-L1, so every pixel feeds all K numerators - still one pass forward and one backward.  K <= 16; no gradient
+    to the masks."""
+
+    @staticmethod
+    def forward(ctx, sr, hr, mask, K):
+        from . import ops
+        sr_c, hr_c, mask_c = sr.contiguous(), hr.contiguous(), mask.detach().contiguous()
+        ctx.save_for_backward(sr_c, hr_c, mask_c)
+        ctx.K = K
+        return ops.loss_sums_soft(sr_c, hr_c, mask_c, K)
+
+    @staticmethod
+    def backward(ctx, dsums):
+        from . import ops
+        sr, hr, mask = ctx.saved_tensors
+        return ops.loss_bwd_soft(sr, hr, mask, dsums.contiguous(), ctx.K), None, None, None
+
+
 def fused_losses(sr, hr, mask_list, trainable_weight, pixel_weight, dynamic_weight, group=None):
-    """l_pix and l_dynamic from one pass over (sr, hr) on the GPU when the masks are one-hot, or None when they are
-    not (the caller then uses the PyTorch formulation).  Same values and gradients as nn.L1Loss +
+    """l_pix and l_dynamic from one pass over (sr, hr) on the GPU: the region-byte kernels when the masks are one-hot, the
+    soft-mask kernels when they are not (contiguous fp32 CUDA masks of at most 16 regions that need no gradient), or None
+    for anything else (the caller then uses the PyTorch formulation; that includes every mask tensor of more than 16
+    regions, one-hot or not, which dasr_mask_compress used to reject with an error from here).  Same values and gradients as nn.L1Loss +
     dynamic_weight_mask_loss('smoothl1'); with a process group the region sums are made global first."""
     from . import ops
     if not sr.is_cuda or sr.dtype != torch.float32 or mask_list.shape[2] == 0:
@@ -73,11 +96,16 @@ def fused_losses(sr, hr, mask_list, trainable_weight, pixel_weight, dynamic_weig
     if H % h or W % w or H // h != W // w:
         return None
     from . import graph, prep
-    if not prep.attach_region(mask_list):     # no-op for masks from prep.depth_to_masks / already checked this step
-        return None
-    region = graph.attached_region(mask_list)
     K = mask_list.shape[1]
-    sums = _RegionSums.apply(sr, hr, region, K)
+    if K > ops.LOSS_MAX_REGIONS:              # beyond the kernels (and beyond dasr_mask_compress): nothing to classify
+        return None
+    if prep.attach_region(mask_list):         # no-op for masks from prep.depth_to_masks / already classified
+        sums = _RegionSums.apply(sr, hr, graph.attached_region(mask_list), K)
+    elif (mask_list.is_cuda and mask_list.dtype == torch.float32 and mask_list.is_contiguous()
+          and not mask_list.requires_grad):
+        sums = _RegionSumsSoft.apply(sr, hr, mask_list, K)
+    else:
+        return None
     num, den, l1 = sums[:K], sums[K:2 * K].detach(), sums[2 * K]
     world = _world(group)
     l_pix = pixel_weight * l1 / sr.numel()
@@ -152,7 +180,10 @@ class Trainer:
         eager steps and replay it afterwards - for steps whose ~2000 launches cost the host more than the GPU needs to run
         them (x8 / 16 frames / bf16: 22-30 ms of enqueue for a 35 ms step).  Single-rank only (the gradient exchange stays
         eager); same-shaped inputs (the loader's tensors are copied into the captured ones); Adam runs in its
-        ``capturable`` form with the learning rate in a device tensor that the scheduler refreshes before every replay."""
+        ``capturable`` form with the learning rate in a device tensor that the scheduler refreshes before every replay.
+        The capture takes the kind of masks of the first captured batch: a step captured on soft masks accepts any later
+        masks of that shape (one-hot included: the general kernels are correct for them), one captured on one-hot masks
+        takes one-hot masks only."""
         self.net = net
         if group is None and torch.distributed.is_available() and torch.distributed.is_initialized():
             group = torch.distributed.group.WORLD
@@ -266,7 +297,9 @@ class Trainer:
         self.update_learning_rate()
         if self._graph is None:
             from . import prep
-            prep.attach_region(masks)              # any host read-back happens before the capture, not inside it
+            # any host read-back happens before the capture, not inside it: the answer (region bytes, or the soft stamp)
+            # stays on the tensor and _step_body / fused_losses ask again for free
+            self._static_soft = not prep.attach_region(masks)
             self._static = (lq, gt, depth, masks)
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
@@ -275,8 +308,8 @@ class Trainer:
             self._graph = g
             self._static_log = self.log
         else:
-            if self._static[3] is not masks:       # region bytes travel with the mask tensor they were derived from
-                from . import graph as _g, ops as _ops, prep as _prep
+            from . import graph as _g, ops as _ops, prep as _prep
+            if self._static[3] is not masks and not self._static_soft:   # region bytes travel with their mask tensor
                 _prep.attach_region(masks)
                 r_new, r_old = _g.attached_region(masks), getattr(self._static[3], "_dasr_region", None)
                 if r_new is None or r_old is None:
@@ -288,7 +321,7 @@ class Trainer:
                         raise ValueError("Trainer(use_graph=True): the captured step has inputs of shape %s, got %s"
                                          % (tuple(dst.shape), tuple(src.shape)))
                     dst.copy_(src)
-            if self._static[3] is not masks:       # the copy bumped the captured mask tensor's version: re-stamp its bytes
+            if self._static[3] is not masks:       # the copy bumped the captured mask tensor's version: re-stamp it
                 self._static[3]._dasr_version = _ops.tensor_version(self._static[3])
         self._graph.replay()
         self.log = self._static_log

@@ -787,3 +787,32 @@ def loss_bwd(sr, hr, region, dsums, K):
     dsr = torch.empty_like(sr)
     _call("dasr_loss_bwd", _p(sr), _p(hr), _lib.ptr(region, dtype=torch.uint8), _p(dsums), _p(dsr), B, C, h, w, H // h, K)
     return dsr
+
+
+# ---- harness losses (soft masks: any float values) ---------------------------------------------
+LOSS_MAX_REGIONS = 16
+
+
+def _soft_loss_dims(sr, mask, K):
+    B, C, H, W = sr.shape
+    Bm, Km, h, w = mask.shape
+    scale = H // h
+    assert (Bm, Km) == (B, K) and H == h * scale and W == w * scale
+    return B, C, h, w, scale
+
+
+def loss_sums_soft(sr, hr, mask, K):
+    """K numerators sum smooth_l1(M_k (sr-hr)) | K areas | sum|sr-hr| for float masks [B,K,h,w] (dasr_loss_sums_soft)."""
+    B, C, h, w, scale = _soft_loss_dims(sr, mask, K)
+    assert hr.shape == sr.shape
+    sums = empty((2 * K + 1,), sr)
+    _call("dasr_loss_sums_soft", _p(sr), _p(hr), _p(mask), _p(sums), B, C, h, w, scale, K)
+    return sums
+
+
+def loss_bwd_soft(sr, hr, mask, dsums, K):
+    B, C, h, w, scale = _soft_loss_dims(sr, mask, K)
+    assert hr.shape == sr.shape and dsums.numel() == 2 * K + 1
+    dsr = torch.empty_like(sr)
+    _call("dasr_loss_bwd_soft", _p(sr), _p(hr), _p(mask), _p(dsums), _p(dsr), B, C, h, w, scale, K)
+    return dsr

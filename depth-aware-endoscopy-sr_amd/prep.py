@@ -1,5 +1,7 @@
 """Device-side input preparation: the depth map is the only per-frame side input that has to
 cross PCIe; the K depth-range planes and the region bytes the one-hot kernels read are derived from it on the GPU.
+Masks from elsewhere are classified once per tensor (``attach_region``: one-hot -> region bytes, else a "soft" stamp;
+``mark_soft`` for a loader that knows) and the answer travels with the tensor until it is edited in place.
 
 Reference counterparts: ``LQGTker_Depth_dataset.getDepthMask`` (codes/data/LQGTker_Depth_dataset.py:204-225), the
 ``_disp.npy`` reader (``:152-154``) and the tensor packing (``:187-199``)."""
@@ -44,19 +46,44 @@ def depth_to_region(depth, num_masks=10, fixed_range=False):
     return ops.depth_to_masks(depth, num_masks, edges, want_planes=False)[1]
 
 
+def _stamp(masks, region, soft):
+    masks._dasr_region = region
+    masks._dasr_soft = soft
+    masks._dasr_version = ops.tensor_version(masks)       # either answer is dropped by an in-place edit (graph.attached_region)
+
+
+def marked_soft(masks):
+    """True while ``masks`` carries a valid "not one-hot" stamp (from ``attach_region`` or ``mark_soft``)."""
+    return bool(getattr(masks, "_dasr_soft", False)) and getattr(masks, "_dasr_version", None) == ops.tensor_version(masks)
+
+
+def mark_soft(masks):
+    """Stamp a mask tensor as "treat as soft": no kernel, no read-back.  Always safe - the general kernels are correct for
+    one-hot masks too, only slower.  A loader that knows its masks are soft calls this and gets a step free of host
+    synchronisation (``attach_region`` then answers False at once).  An in-place edit of the tensor drops the stamp."""
+    _stamp(masks, None, True)
+    return masks
+
+
 def attach_region(masks):
     """Give a mask tensor that did NOT come from ``depth_to_masks`` (e.g. the reference's CPU dataloader output moved to
     the GPU) its region bytes, so that the generator and the fused loss take the one-hot kernels without ever reading
     a flag back mid-step.  Costs one compression pass and ONE 4-byte read-back, here, before any of the step's work is
-    queued.  Returns True when the masks are one-hot (region attached), False for soft / overlapping masks."""
+    queued.  Returns True when the masks are one-hot (region attached), False for soft / overlapping masks.
+
+    Either answer is remembered on the tensor, stamped with its version: a second call on the same unmodified tensor
+    launches nothing and reads nothing back, so the harness may ask again (and may ask inside a graph capture once it has
+    asked before it).  A tensor stamped by ``mark_soft`` answers False without ever being looked at."""
     from . import graph
     if graph.attached_region(masks) is not None:
         return True
+    if marked_soft(masks):
+        return False
     if not masks.is_cuda or masks.dtype != torch.float32 or not masks.is_contiguous():
         return False
     region, flag = ops.mask_compress(masks)
     if int(flag.item()) != 0:
+        _stamp(masks, None, True)
         return False
-    masks._dasr_region = region
-    masks._dasr_version = ops.tensor_version(masks)
+    _stamp(masks, region, False)
     return True

@@ -337,7 +337,7 @@ size_t dasr_depth_to_masks_workspace(int B, int HW);
 int dasr_depth_to_masks(const float* depth, const float* fixed_edges, float* masks, unsigned char* region,
                         void* workspace, size_t workspace_bytes, int B, int HW, int K, void* stream);
 
-/* ---- harness losses in one pass (one-hot masks only) -------------------------------------
+/* ---- harness losses in one pass (one-hot and soft masks) ----------------------------------
  * nn.L1Loss + dynamic_weight_mask_loss('smoothl1') (F_model_depthCond.py:164,188-190; mask_loss.py:64-90) need, per
  * depth region k, sum smooth_l1(m_k*sr, m_k*hr) and sum m_k (masks nearest-upsampled to HR), and sum |sr-hr|.
  * sr, hr: NCHW [B,C,h*scale,w*scale]; region: bytes [B,h,w] from dasr_mask_compress.
@@ -347,6 +347,17 @@ int dasr_loss_sums(const float* sr, const float* hr, const unsigned char* region
                    int w, int scale, int K, void* stream);
 int dasr_loss_bwd(const float* sr, const float* hr, const unsigned char* region, const float* dsums, float* dsr, int B,
                   int C, int h, int w, int scale, int K, void* stream);
+/* The same sums for arbitrary float masks (negative values, zeros, values above 1; not one-hot): replaces the K masked
+ * passes of dynamic_weight_mask_loss('smoothl1') (mask_loss.py:64-90) and nn.L1Loss (F_model_depthCond.py:164,188-190).
+ * mask: NCHW [B,K,h,w] float32, nearest-upsampled by `scale` to M_k; d = sr - hr.
+ * sums [2K+1], the layout of dasr_loss_sums: num_k = sum smooth_l1(M_k * d) (beta 1; the mask is INSIDE the
+ * smooth-L1) | area_k = C * scale^2 * sum m_k | sum |d|.  K <= 16, else DASR_E_UNSUPPORTED.
+ * dasr_loss_bwd_soft: dsr = dsums[2K]*sign(d) + sum_k dsums[k] * M_k * smooth_l1'(M_k * d); dsums[K..2K-1] is not read
+ * (the harness detaches the areas) and the masks receive no gradient. */
+int dasr_loss_sums_soft(const float* sr, const float* hr, const float* mask, float* sums, int B, int C, int h, int w,
+                        int scale, int K, void* stream);
+int dasr_loss_bwd_soft(const float* sr, const float* hr, const float* mask, const float* dsums, float* dsr, int B, int C,
+                       int h, int w, int scale, int K, void* stream);
 
 /* ---- small elementwise helpers ---------------------------------------------------------------- */
 int dasr_add(const float* a, const float* b, float* out, size_t n, void* stream);  /* torch.add, sftmd_arch.py:931 */

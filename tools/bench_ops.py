@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Per-op timing on the GPU (HIP events on the launch stream): SEAN fwd/bwd and the hot conv shapes.
-Usage: python tools/bench_ops.py [--batch 16] [--iters 10] [--soft]
+Usage: python tools/bench_ops.py [--batch 16] [--iters 10] [--soft] [--only loss]
+--only loss: the harness-loss kernels at the c2 size (3 x 1024 x 1280 HR, K = 10, scale 8): the one-hot pair, the soft pair on the
+same one-hot-valued masks and on truly soft ones, and the PyTorch formulation on the soft masks; five rounds each.
 --soft: SEAN only; adds forward and backward through the general (soft-mask) path, on the one-hot-valued masks and on a truly
 soft mask (0.7*mk + 0.3*rand: all 9*K terms of the dynamic convolution live)."""
 import argparse
@@ -24,6 +26,49 @@ def timeit(fn, iters):
     e1.record()
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) / iters * 1e3  # us
+
+
+def bench_loss(a, dev, rounds=5):
+    """One-hot and soft loss kernels and the PyTorch formulation, forward and backward, median (min .. max) of ``rounds``
+    windows of ``--iters`` calls.  GB/s = the bytes the algorithm needs (forward: sr + hr and the LR planes / region bytes;
+    backward: + dsr) over the time."""
+    from dasr_amd import harness
+    B, K, s, h, w = a.batch, 10, 8, 128, 160
+    H, W = h * s, w * s
+    mk = synth.seeded_batch(0, B, h, w, 1, K)[3].to(dev).contiguous()
+    soft = (0.7 * mk + 0.3 * torch.rand(mk.shape, device=dev)).contiguous()
+    hr = torch.rand(B, 3, H, W, device=dev)
+    sr = (hr + 0.6 * torch.randn(B, 3, H, W, device=dev)).clamp(-1, 2)
+    region, flag = ops.mask_compress(mk)
+    assert int(flag.item()) == 0
+    dsums = torch.rand(2 * K + 1, device=dev) + 0.5
+    img = B * 3 * H * W * 4
+
+    def row(name, fn, nbytes=None):
+        ts = sorted(timeit(fn, a.iters) for _ in range(rounds))
+        med = ts[len(ts) // 2]
+        bw = "  %7.1f GB/s" % (nbytes / med / 1e3) if nbytes else ""
+        print("%-44s %9.1f us (%.1f .. %.1f)%s" % (name, med, ts[0], ts[-1], bw), flush=True)
+        return med
+
+    row("loss_sums      one-hot (region bytes)", lambda: ops.loss_sums(sr, hr, region, K), 2 * img + B * h * w)
+    row("loss_bwd       one-hot (region bytes)", lambda: ops.loss_bwd(sr, hr, region, dsums, K), 3 * img + B * h * w)
+    for name, m in (("one-hot-valued", mk), ("truly soft", soft)):
+        row("loss_sums_soft %s" % name, lambda: ops.loss_sums_soft(sr, hr, m, K), 2 * img + m.numel() * 4)
+        row("loss_bwd_soft  %s" % name, lambda: ops.loss_bwd_soft(sr, hr, m, dsums, K), 3 * img + m.numel() * 4)
+    loss = harness.DynamicMaskLoss(K).to(dev)
+    srg = sr.clone().requires_grad_(True)
+
+    def torch_fwd():
+        return torch.nn.functional.l1_loss(srg, hr) + loss(srg, hr, soft)[2]
+
+    def torch_fwd_bwd():
+        srg.grad = None
+        torch_fwd().backward()
+
+    f = row("PyTorch formulation, soft masks: forward", torch_fwd)
+    fb = row("PyTorch formulation, soft masks: fwd + bwd", torch_fwd_bwd)
+    print("%-44s %9.1f us" % ("PyTorch formulation, soft masks: backward", fb - f))
 
 
 def main():
@@ -79,6 +124,8 @@ def main():
                 us = timeit(lambda: ops.sean_bwd(dout, o, t, mean, var, gb2, m, None, None, D, bg, bb, ag, ab, True, True),
                             a.iters)
                 print("sean_bwd     general path, %-14s %8.1f us" % (name, us))
+    if not a.only or "loss" in a.only:
+        bench_loss(a, dev)
     if not a.only or "dynk" in a.only:
         L = 256
         st = torch.randn(B, K, L, device=dev)
