@@ -153,6 +153,18 @@ static inline u32x4_t dasr_buffer_load16(const BufRsrc& r, unsigned off) {
     if ((size_t)off + 16 <= r.bytes) memcpy(&v, r.base + off, 16);
     return v;
 }
+// 4-byte load / 4- and 16-byte stores through the same range check (an out-of-range store is dropped)
+static inline float dasr_buffer_load4f(const BufRsrc& r, unsigned off) {
+    float v = 0.f;
+    if ((size_t)off + 4 <= r.bytes) memcpy(&v, r.base + off, 4);
+    return v;
+}
+static inline void dasr_buffer_store4f(const BufRsrc& r, unsigned off, float v) {
+    if ((size_t)off + 4 <= r.bytes) memcpy(const_cast<char*>(r.base) + off, &v, 4);
+}
+static inline void dasr_buffer_store16f(const BufRsrc& r, unsigned off, float4 v) {
+    if ((size_t)off + 16 <= r.bytes) memcpy(const_cast<char*>(r.base) + off, &v, 16);
+}
 #else
 typedef __amdgpu_buffer_rsrc_t BufRsrc;
 __device__ __forceinline__ BufRsrc dasr_make_rsrc(const void* p, size_t bytes) {
@@ -160,5 +172,15 @@ __device__ __forceinline__ BufRsrc dasr_make_rsrc(const void* p, size_t bytes) {
 }
 __device__ __forceinline__ u32x4_t dasr_buffer_load16(BufRsrc r, unsigned off) {
     return __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
+}
+// 4-byte load / 4- and 16-byte stores through the same range check (an out-of-range store is dropped)
+__device__ __forceinline__ float dasr_buffer_load4f(BufRsrc r, unsigned off) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)off, 0, 0));
+}
+__device__ __forceinline__ void dasr_buffer_store4f(BufRsrc r, unsigned off, float v) {
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, (int)off, 0, 0);
+}
+__device__ __forceinline__ void dasr_buffer_store16f(BufRsrc r, unsigned off, float4 v) {
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), r, (int)off, 0, 0);
 }
 #endif

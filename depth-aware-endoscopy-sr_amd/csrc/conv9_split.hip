@@ -10,9 +10,9 @@
 //   wgrad:    dW[kh][k'][ci] = sum_q x[q][ci] * E[q.y-kh+4][q.x][k']                         M = ci, N = 27, K = pixels
 // with k' = Cout*(8-kw) + co and E[row][px][k'] = the 27 consecutive values of the 3-channel dy row starting at pixel px-4.
 // Everything that is an MFMA operand lives in LDS as TWO fp16 images (value and what the first rounding left), so tiles are
-// half the size of the bf16 kernels': the forward walks 16-channel chunks of an 8 x 56 pixel tile, dgrad / wgrad 8 x 32 tiles.
-// All three kernels are persistent (one 512-thread workgroup per CU, kernel images staged once) and hold the next tile's
-// global loads in registers while the current one is multiplied.
+// half the size of the bf16 kernels': the forward walks 16-channel chunks of an 8 x 56 pixel tile, the wgrad 8 x 32 tiles, the
+// dgrad 8 x 16 tiles.  All three kernels are persistent (forward / wgrad: one 512-thread workgroup per CU, dgrad: two of 256;
+// kernel images staged once) and hold the next tile's global loads in registers while the current one is multiplied.
 #include "bf16.h"
 #include "conv_kernels.h"
 
@@ -33,6 +33,9 @@ struct Conv9SplitArgs {
     const float* wmax;   // ... and the kernel (fwd / dgrad)
     int B, H, W, Cin, Cout;
     int accumulate, P, ntiles;
+    const float* xact;   // fused dgrad: the convolution's saved input (the producer's activated, shuffled output) ...
+    float* amax;         // ... the amax buffer of dprev (may be NULL) ...
+    int act;             // ... and the producer's activation
 };
 
 // ---- scales: the maximum of an amax buffer's parts, by the whole workgroup (phase 1 before a barrier, phase 2 after it)
@@ -277,102 +280,242 @@ __device__ __forceinline__ void s9_fetch_dy(const Conv9SplitArgs& a, int b, int 
 }
 
 // ------------------------------------------------------------------------------------------ dgrad
-// tile: 8 rows x 32 columns of dx pixels x 32 input channels (blockIdx.y selects the 32-channel slice); wave w owns tile row w
-// (one 32-pixel M-tile): 9 kh x 2 K-halves x 3 products = 54 MFMAs per wave and tile.
-__global__ void __launch_bounds__(512) k_conv9_dgrad_split(Conv9SplitArgs a) {
+// 256 threads, TWO workgroups per CU (74.9 KB of LDS each) whose phases overlap: while one stages dy / builds its E image /
+// stores, the other multiplies.  tile: 8 rows x 16 columns of dx pixels x 32 input channels (blockIdx.y selects the
+// 32-channel slice); wave w owns tile rows 2w, 2w+1 as ONE 32-pixel M-tile, lane li = row li >> 4, column li & 15:
+// 9 kh x 2 K-halves x 3 products = 54 MFMAs per wave and tile, the K order of every output element what it always was.
+// With the accumulator map row = (reg&3) + 8(reg>>2) + 4(lane>>5), registers g and g + 8 hold image rows 2w and 2w+1 of one
+// column, g&3 = 0,1 / 2,3 two even/odd column pairs: a lane owns the complete 2 x 2 blocks of its channel.
+// FUSE: the producer's activation / PixelShuffle(2) backward in the epilogue - x_act = this convolution's saved input (the
+// producer's post-activation, shuffled output), dprev[b][y/2][x/2][4c + 2(y&1) + (x&1)] = dx[b][y][x][c] * act'(x_act): one
+// float4 per 2 x 2 block, the 32 channel lanes of a half-wave write 512 contiguous bytes - and max |dprev| for the
+// producer's own gradients (amax buffer, one word per workgroup).
+// LDS: E as 2 x [16 rows][16 px][32 k'] and Wd as 2 x [9 kh][32 ci][32 k'] fp16, 64-byte pixel / channel stride with the
+// 16-byte piece index XORed with (px >> 2) & 3 resp. (ci >> 2) & 3: each 16-lane group of a ds_read_b128 (MI355X: lanes
+// {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} of a half-wave) meets the pieces 0..3 of every bank quarter once.
+// Global stores and the x_act loads go through range-checked buffer descriptors (ragged tiles: DASR_OOB, dropped), so every
+// wave issues the same number of vector-memory operations per tile and the barriers are LDS-only: stores drain under the
+// next tile's work instead of at its first barrier.
+#define S9D_TQ 16
+#define S9D_DYW ((S9D_TQ + 8) * 3 + 8)    // dy tile row stride: 24 px * 3 ch + pad = 80 (E pieces read up to element 3*15 + 31 + 2)
+constexpr int S9D_NDYE = (S9_TH + 8) * S9D_DYW, S9D_NDI = S9D_NDYE / 256;
+static_assert(S9D_NDI * 256 == S9D_NDYE, "dy tile: whole trips of 256 threads");
+constexpr size_t S9D_LDS = sizeof(h16_t) * (size_t)(2 * (S9_TH + 8) * S9D_TQ * 32 + 2 * 9 * 32 * 32) + sizeof(float) * (size_t)(S9D_NDYE + 32);     // (the dy tile: two fp16 images)
+static_assert(2 * S9D_LDS <= 160 * 1024, "two workgroups per CU");
+typedef unsigned u32a_t __attribute__((may_alias));
+typedef unsigned u32x4a_t __attribute__((ext_vector_type(4), may_alias));
+// the low dword of {hi, lo} >> bits (bits = 0 or 16: eight fp16 from any element offset out of aligned dword reads)
+__device__ __forceinline__ unsigned s9d_fsh(unsigned lo, unsigned hi, unsigned bits) {
+#if DASR_DEVICE_BUILD
+    return __builtin_amdgcn_alignbit(hi, lo, bits);
+#else
+    return (unsigned)((((unsigned long long)hi << 32) | lo) >> bits);
+#endif
+}
+template <bool FUSE>
+__global__ void __launch_bounds__(256, 2) k_conv9_dgrad_split(Conv9SplitArgs a) {
     DASR_DYN_SMEM(smem);
-    constexpr int EST = 40;                                        // 80-byte pixel stride (conflict-free ds_read_b128)
-    constexpr int NE = (S9_TH + 8) * S9_TQ * EST;
-    h16_t* sE0 = (h16_t*)smem;                                     // [16][32][EST]
+    constexpr int NE = (S9_TH + 8) * S9D_TQ * 32;
+    h16_t* sE0 = (h16_t*)smem;                                     // [16][16][32], pieces swizzled
     h16_t* sE1 = sE0 + NE;
-    h16_t* sW0 = sE1 + NE;                                         // [9 kh][32 ci][EST]: Wd[kh][k'][ci], k' contiguous
-    h16_t* sW1 = sW0 + 9 * 32 * EST;
-    float* sDy = (float*)(sW1 + 9 * 32 * EST);                     // [16][DYW]
-    float* s_red = sDy + S9_NDYE;                                  // [32]
+    h16_t* sW0 = sE1 + NE;                                         // [9 kh][32 ci][32]: Wd[kh][k'][ci], k' contiguous, pieces swizzled
+    h16_t* sW1 = sW0 + 9 * 32 * 32;
+    h16_t* sH0 = sW1 + 9 * 32 * 32;                                // [16][DYW]: the dy tile, split ONCE per value
+    h16_t* sH1 = sH0 + S9D_NDYE;
+    float* s_red = (float*)(sH1 + S9D_NDYE);                       // [32]
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, li = lane & 31, lh = lane >> 5;
-    const int tiles_x = (a.W + S9_TQ - 1) / S9_TQ, tiles_y = (a.H + S9_TH - 1) / S9_TH;
+    const int tiles_x = (a.W + S9D_TQ - 1) / S9D_TQ, tiles_y = (a.H + S9_TH - 1) / S9_TH;
     const int total = tiles_x * tiles_y * a.B;
     const int n0 = blockIdx.y * 32;
     const int KK = 9 * a.Cout;
     int kd, kw_;
     s9_scales(a.dmax, a.wmax, s_red, kd, kw_);
     const float sd = s9_pow2(kd), sw = s9_pow2(kw_), inv = s9_pow2(-(kd + kw_));
-    {                                                              // Wd[kh][k'][ci] = w[kh][8 - k'/Cout][ci][k' % Cout], once
+#pragma unroll 1
+    for (int h = 0; h < 2; ++h) {                                  // Wd[kh][k'][ci] = w[kh][8 - k'/Cout][ci][k' % Cout], once
         float wq[18];
 #pragma unroll
         for (int u = 0; u < 18; ++u) {
-            const int e = tid + 512 * u, kp = e & 31, ci = (e >> 5) & 31, kh = e >> 10;
+            const int e = tid + 256 * (18 * h + u), kp = e & 31, ci = (e >> 5) & 31, kh = e >> 10;
             const int kq = kp < KK ? kp : 0, kw = 8 - kq / a.Cout, co = kq % a.Cout;
             const float v = a.w[(((size_t)kh * 9 + kw) * a.Cin + n0 + ci) * a.Cout + co];
             wq[u] = kp < KK ? v : 0.f;
         }
 #pragma unroll
         for (int u = 0; u < 18; ++u) {
-            const int e = tid + 512 * u, kp = e & 31, ci = (e >> 5) & 31, kh = e >> 10;
+            const int e = tid + 256 * (18 * h + u), kp = e & 31, ci = (e >> 5) & 31, kh = e >> 10;
             h16_t h0, h1;
             s9_split(wq[u], sw, h0, h1);
-            sW0[(kh * 32 + ci) * EST + kp] = h0;
-            sW1[(kh * 32 + ci) * EST + kp] = h1;
+            const int o = (kh * 32 + ci) * 32 + 8 * ((kp >> 3) ^ ((ci >> 2) & 3)) + (kp & 7);
+            sW0[o] = h0;
+            sW1[o] = h1;
         }
     }
-    float vdy[S9_NDI];
+    // dy tile, rows y0-4 .. y0+11, columns x0-4 .. x0+19, Cout channels interleaved: element tid + 256 u is float f of tile row
+    // ry - what does not depend on the tile is worked out once (the divisions by Cout above all)
+    int dyr[S9D_NDI], dyx[S9D_NDI], dyo[S9D_NDI];
+#pragma unroll
+    for (int u = 0; u < S9D_NDI; ++u) {
+        const int idx = tid + 256 * u, f = idx % S9D_DYW, ry = idx / S9D_DYW;
+        dyr[u] = ry - 4;
+        dyx[u] = f < (S9D_TQ + 8) * a.Cout ? f / a.Cout - 4 : (1 << 28);       // (the row's padding: never inside the image)
+        dyo[u] = (dyr[u] * a.W - 4) * a.Cout + f;                             // floats from the tile's origin pixel (y0, x0)
+    }
+    float vdy[S9D_NDI];
     auto origin = [&](int tile, int& b, int& x0, int& y0) {
         b = tile / (tiles_x * tiles_y);
         const int tt = tile - b * (tiles_x * tiles_y);
-        x0 = (tt % tiles_x) * S9_TQ;
+        x0 = (tt % tiles_x) * S9D_TQ;
         y0 = (tt / tiles_x) * S9_TH;
     };
+    // the next tile's dy values stay in flight in registers (zero outside the image: the descriptor's range check)
+    auto fetch = [&](int b, int y0, int x0) {
+        const BufRsrc rd = dasr_make_rsrc(a.dy + (size_t)b * a.H * a.W * a.Cout, (size_t)a.H * a.W * a.Cout * sizeof(float));
+        const int base = (y0 * a.W + x0) * a.Cout;
+#pragma unroll
+        for (int u = 0; u < S9D_NDI; ++u) {
+            const bool ok = (unsigned)(y0 + dyr[u]) < (unsigned)a.H && (unsigned)(x0 + dyx[u]) < (unsigned)a.W;
+            vdy[u] = dasr_buffer_load4f(rd, ok ? (unsigned)((base + dyo[u]) * (int)sizeof(float)) : DASR_OOB);
+        }
+    };
+    const int prow = 2 * wv + (li >> 4), pcol = li & 15;            // this lane's pixel as the A operand's row
+    const int asw = (pcol >> 2) & 3, bsw = (li >> 2) & 3;
+    // E[row][px][k'] = dy row image [Cout px + k'] (0 for k' >= 9 Cout), 16-byte pieces (row, px, 8 k'): this thread builds
+    // the piece (px, p8) of rows r0, r0 + 4, .. - eight fp16 from element es of the row, any parity, out of five aligned dwords
+    const int p8 = tid & 3, epx = (tid >> 2) & 15, r0 = tid >> 6;
+    const int es = a.Cout * epx + 8 * p8;
+    const unsigned ebits = (es & 1) * 16;
+    const int esrc = r0 * S9D_DYW + (es & ~1), edst = (r0 * S9D_TQ + epx) * 32 + 8 * (p8 ^ ((epx >> 2) & 3));
+    unsigned em[4];
+#pragma unroll
+    for (int d = 0; d < 4; ++d) em[d] = (8 * p8 + 2 * d < KK ? 0xffffu : 0u) | (8 * p8 + 2 * d + 1 < KK ? 0xffff0000u : 0u);
+    const size_t img = (size_t)a.H * a.W * a.Cin;                  // floats per sample of dx, x_act and dprev alike
+    const unsigned rowst = (unsigned)(a.W * a.Cin) * sizeof(float), pixst = (unsigned)a.Cin * sizeof(float);
+    // dasr_act_grad_from_out(v, act) = v > 0 ? 1 : dneg for the three activations the entry point admits
+    const float dneg = a.act == DASR_ACT_RELU ? 0.f : (a.act == DASR_ACT_LRELU02 ? 0.2f : 1.f);
+    float om = 0.f;
     int tile = blockIdx.x;
     if (tile < total) {
         int b, x0, y0;
         origin(tile, b, x0, y0);
-        s9_fetch_dy(a, b, y0, x0, tid, vdy);
+        fetch(b, y0, x0);
     }
     for (; tile < total; tile += gridDim.x) {
         int b, x0, y0;
         origin(tile, b, x0, y0);
-        __syncthreads();                                           // every wave is done with the previous tile's E image
+        // (no barrier here: the row images were last read before the previous tile's second barrier, and E is written after this
+        // tile's first)
 #pragma unroll
-        for (int u = 0; u < S9_NDI; ++u) {
-            const int idx = tid + 512 * u;
-            if (idx < S9_NDYE) sDy[idx] = vdy[u];
+        for (int u = 0; u < S9D_NDI; ++u) {
+            h16_t h0, h1;
+            s9_split(vdy[u], sd, h0, h1);
+            sH0[tid + 256 * u] = h0;
+            sH1[tid + 256 * u] = h1;
         }
-        __syncthreads();
+        DASR_LDS_BARRIER();                                        // ... which every wave reaches after its K loop over E
         {
             int nb, nx0, ny0;
             origin(tile + (int)gridDim.x < total ? tile + (int)gridDim.x : tile, nb, nx0, ny0);
-            s9_fetch_dy(a, nb, ny0, nx0, tid, vdy);
+            fetch(nb, ny0, nx0);
         }
-        s9_build_E<EST>(a, sDy, sE0, sE1, sd, tid);
-        __syncthreads();
+        // byte offsets of this lane's pixels in dx / x_act (one layout): column pairs 4 lh + {0, 2, 8, 10} of image row
+        // y0 + 2 wv; + pixst: the odd column, + rowst: the row below (fused form, H and W even: a 2 x 2 block is inside or outside
+        // as a whole; DASR_OOB + those stays out of range)
+        unsigned xoff[4];
+        const bool rowok = y0 + 2 * wv < a.H;
+#pragma unroll
+        for (int cp = 0; cp < 4; ++cp) {
+            const int cx = x0 + 4 * lh + 2 * (cp & 1) + 8 * (cp >> 1);
+            xoff[cp] = (rowok && cx < a.W) ? (unsigned)((((y0 + 2 * wv) * a.W + cx) * a.Cin + n0 + li) * (int)sizeof(float)) : DASR_OOB;
+        }
+        auto pix_off = [&](int g) {      // accumulator register g: image row (g >> 3), column (g & 3) + 8 ((g >> 2) & 1) + 4 lh
+            const unsigned o = xoff[((g >> 2) & 1) * 2 + ((g & 3) >> 1)] + (g >> 3) * rowst + (g & 1) * pixst;
+            if (FUSE) return o;
+            // (the plain form takes odd H and W: the lower row / the odd column can be outside on its own)
+            return (y0 + 2 * wv + (g >> 3) < a.H && x0 + 4 * lh + (g & 3) + 8 * ((g >> 2) & 1) < a.W) ? o : DASR_OOB;
+        };
+        float xa[16];
+        if (FUSE) {                                                // in flight across the E build and the K loop
+            const BufRsrc rx = dasr_make_rsrc(a.xact + (size_t)b * img, img * sizeof(float));
+#pragma unroll
+            for (int g = 0; g < 16; ++g) xa[g] = dasr_buffer_load4f(rx, pix_off(g));
+        }
+#pragma unroll
+        for (int i = 0; i < (S9_TH + 8) / 4; ++i) {
+            const u32a_t* s0 = (const u32a_t*)(sH0 + esrc + i * 4 * S9D_DYW);
+            const u32a_t* s1 = (const u32a_t*)(sH1 + esrc + i * 4 * S9D_DYW);
+            u32x4_t o0, o1;
+#pragma unroll
+            for (int d = 0; d < 4; ++d) {
+                o0[d] = s9d_fsh(s0[d], s0[d + 1], ebits) & em[d];
+                o1[d] = s9d_fsh(s1[d], s1[d + 1], ebits) & em[d];
+            }
+            *(u32x4a_t*)(sE0 + edst + i * 4 * S9D_TQ * 32) = o0;
+            *(u32x4a_t*)(sE1 + edst + i * 4 * S9D_TQ * 32) = o1;
+        }
+        DASR_LDS_BARRIER();
         f32x16 acc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        {
+            // step s = (kh, K-half q): the operands of step s + 1 are read while step s multiplies
+            // dy row of output row prow for this kh: prow - kh + 4 (+4 for the tile's first row y0-4) = prow - kh + 8
+            const int wb = li * 32, eb = ((prow + 8) * S9D_TQ + pcol) * 32;
+            const int pw0 = 8 * (lh ^ bsw), pw1 = 8 * ((2 + lh) ^ bsw), pe0 = 8 * (lh ^ asw), pe1 = 8 * ((2 + lh) ^ asw);
+            h16x8 A0 = *(const h16x8*)(sE0 + eb + pe0), A1 = *(const h16x8*)(sE1 + eb + pe0);
+            h16x8 B0 = *(const h16x8*)(sW0 + wb + pw0), B1 = *(const h16x8*)(sW1 + wb + pw0);
+            DASR_SCHED_BARRIER();
 #pragma unroll
-        for (int kh = 0; kh < 9; ++kh)
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const int wo = (kh * 32 + li) * EST + 16 * q + 8 * lh;
-                const h16x8 B0 = *(const h16x8*)(sW0 + wo), B1 = *(const h16x8*)(sW1 + wo);
-                // dy row of output row wv for this kh: wv - kh + 4 (+4 for the tile's first row y0-4) = wv - kh + 8
-                const int eo = ((wv - kh + 8) * S9_TQ + li) * EST + 16 * q + 8 * lh;
-                const h16x8 A0 = *(const h16x8*)(sE0 + eo), A1 = *(const h16x8*)(sE1 + eo);
-                acc = s9_mma(A0, A1, B0, B1, acc);
+            for (int s = 0; s < 18; ++s) {
+                const h16x8 a0 = A0, a1 = A1, b0 = B0, b1 = B1;
+                if (s + 1 < 18) {
+                    const int kh = (s + 1) >> 1, q = (s + 1) & 1;
+                    const int wo = wb + kh * 32 * 32 + (q ? pw1 : pw0), eo = eb - kh * S9D_TQ * 32 + (q ? pe1 : pe0);
+                    A0 = *(const h16x8*)(sE0 + eo); A1 = *(const h16x8*)(sE1 + eo);
+                    B0 = *(const h16x8*)(sW0 + wo); B1 = *(const h16x8*)(sW1 + wo);
+                }
+                acc = s9_mma(a0, a1, b0, b1, acc);
+                if (s + 1 < 18) DASR_SCHED_GROUP(0x100, 4);        // (hipcc otherwise sinks the reads to just before their use)
+                DASR_SCHED_GROUP(0x8, 3);
             }
-        float* dx = (float*)a.out;
-        const int gy = y0 + wv;
-        if (gy < a.H) {
+            DASR_SCHED_BARRIER();                                  // (... and hoists the epilogue's use of x_act into the loop)
+        }
+        if (FUSE) {
+            const BufRsrc rp = dasr_make_rsrc((float*)a.out + (size_t)b * img, img * sizeof(float));
+            const int Wc = a.W >> 1, cy = (y0 >> 1) + wv;
 #pragma unroll
-            for (int g = 0; g < 16; ++g) {
-                const int gx = x0 + (g & 3) + 8 * (g >> 2) + 4 * lh;
-                if (gx >= a.W) continue;
-                const size_t o = (((size_t)b * a.H + gy) * a.W + gx) * a.Cin + n0 + li;
-                float v = acc[g] * inv;
-                if (a.accumulate) v += dx[o];
-                dx[o] = v;
+            for (int j = 0; j < 4; ++j) {
+                const int g = 2 * (j & 1) + 4 * (j >> 1);          // 0, 2, 4, 6: column pair j, image rows 2 wv (g, g + 1) and 2 wv + 1 (g + 8, g + 9)
+                const int cx = x0 + 4 * lh + 2 * (j & 1) + 8 * (j >> 1);
+                const bool ok = xoff[j] != DASR_OOB;
+                float4 o;
+                o.x = acc[g] * inv * (xa[g] > 0.f ? 1.f : dneg);
+                o.y = acc[g + 1] * inv * (xa[g + 1] > 0.f ? 1.f : dneg);
+                o.z = acc[g + 8] * inv * (xa[g + 8] > 0.f ? 1.f : dneg);
+                o.w = acc[g + 9] * inv * (xa[g + 9] > 0.f ? 1.f : dneg);
+                dasr_buffer_store16f(rp, ok ? (unsigned)(((cy * Wc + (cx >> 1)) * (4 * a.Cin) + 4 * (n0 + li)) * (int)sizeof(float)) : DASR_OOB, o);
+                om = fmaxf(om, ok ? dasr_amax4(0.f, o) : 0.f);
+            }
+        } else {
+            const BufRsrc ro = dasr_make_rsrc((float*)a.out + (size_t)b * img, img * sizeof(float));
+            if (a.accumulate) {
+                float old[16];
+#pragma unroll
+                for (int g = 0; g < 16; ++g) old[g] = dasr_buffer_load4f(ro, pix_off(g));
+#pragma unroll
+                for (int g = 0; g < 16; ++g) {
+                    float v = acc[g] * inv;
+                    v += old[g];
+                    dasr_buffer_store4f(ro, pix_off(g), v);
+                }
+            } else {
+#pragma unroll
+                for (int g = 0; g < 16; ++g) dasr_buffer_store4f(ro, pix_off(g), acc[g] * inv);
             }
         }
     }
+    // every thread of every workgroup arrives (the grid never exceeds the tile count: no workgroup is idle)
+    if (FUSE && a.amax) dasr_amax_commit(a.amax, om, s_red, dasr_flat_wg(), dasr_flat_nwg());
 }
 
 // ------------------------------------------------------------------------------------------ wgrad
@@ -527,15 +670,26 @@ int conv9_split_fwd(const ConvGeom& g, const float* x, const float* xmax, const 
     DASR_LAUNCH(k_conv9_fwd_split, dim3(tiles < cap ? tiles : cap), dim3(512), lds, stream, a);     // one persistent workgroup per CU
     DASR_RETURN_LAUNCH_STATUS();
 }
+static int conv9_split_dgrad_launch(const ConvGeom& g, Conv9SplitArgs& a, bool fuse, void* stream) {
+    const int tiles = ((g.W + S9D_TQ - 1) / S9D_TQ) * ((g.H + S9_TH - 1) / S9_TH) * g.B;
+    int per = 512 / (g.Cin / 32) > 0 ? 512 / (g.Cin / 32) : 1;               // persistent: two workgroups per CU over all slices
+    if ((dasr_get_conv_bf16_impl() & 3) == 2) per = 3;
+    const dim3 grid(tiles < per ? tiles : per, g.Cin / 32);
+    if (fuse)
+        DASR_LAUNCH(k_conv9_dgrad_split<true>, grid, dim3(256), S9D_LDS, stream, a);
+    else
+        DASR_LAUNCH(k_conv9_dgrad_split<false>, grid, dim3(256), S9D_LDS, stream, a);
+    DASR_RETURN_LAUNCH_STATUS();
+}
 int conv9_split_dgrad(const ConvGeom& g, const float* dconv, const float* dmax, const float* w, const float* wmax, float* dx,
                       int accumulate, void* stream) {
     Conv9SplitArgs a{nullptr, w, nullptr, dconv, dx, nullptr, dmax, wmax, g.B, g.H, g.W, g.Cin, g.Cout, accumulate, 0, 0};
-    const int tiles = ((g.W + S9_TQ - 1) / S9_TQ) * ((g.H + S9_TH - 1) / S9_TH) * g.B;
-    const size_t lds = sizeof(h16_t) * (size_t)(2 * (S9_TH + 8) * S9_TQ * 40 + 2 * 9 * 32 * 40) + sizeof(float) * (size_t)(S9_NDYE + 32);
-    int per = 256 / (g.Cin / 32) > 0 ? 256 / (g.Cin / 32) : 1;               // persistent: one workgroup per CU over all slices
-    if ((dasr_get_conv_bf16_impl() & 3) == 2) per = 3;
-    DASR_LAUNCH(k_conv9_dgrad_split, dim3(tiles < per ? tiles : per, g.Cin / 32), dim3(512), lds, stream, a);
-    DASR_RETURN_LAUNCH_STATUS();
+    return conv9_split_dgrad_launch(g, a, false, stream);
+}
+int conv9_split_dgrad_act(const ConvGeom& g, const float* dconv, const float* dmax, const float* w, const float* wmax,
+                          const float* x_act, float* dprev, float* amax, int act, void* stream) {
+    Conv9SplitArgs a{nullptr, w, nullptr, dconv, dprev, nullptr, dmax, wmax, g.B, g.H, g.W, g.Cin, g.Cout, 0, 0, 0, x_act, amax, act};
+    return conv9_split_dgrad_launch(g, a, true, stream);
 }
 static void conv9_split_wgrad_plan(const ConvGeom& g, int& ntiles, int& P) {
     ntiles = g.B * ((g.H + S9_TH - 1) / S9_TH) * ((g.W + S9_TQ - 1) / S9_TQ);
@@ -588,6 +742,17 @@ extern "C" int dasr_conv9_dgrad_split2(const float* dconv, const float* dmax, co
     if (!dasr_conv9_split_supported(H, W, Cin, Cout)) return DASR_E_UNSUPPORTED;
     ConvGeom g{B, H, W, Cin, H, W, Cout, 9, 9, 1, 4, 0};
     return conv9_split_dgrad(g, dconv, dmax, w_hwio, wmax, dx, accumulate, stream);
+}
+extern "C" int dasr_conv9_dgrad_act_split2(const float* dconv, const float* dmax, const float* w_hwio, const float* wmax,
+                                           const float* x_act, float* dprev, float* amax, int B, int H, int W, int Cin, int Cout,
+                                           int act, int ps_r, void* stream) {
+    DASR_CHECK_PTR(dconv); DASR_CHECK_PTR(dmax); DASR_CHECK_PTR(w_hwio); DASR_CHECK_PTR(wmax); DASR_CHECK_PTR(x_act); DASR_CHECK_PTR(dprev);
+    DASR_CHECK_SHAPE(B > 0);
+    if (ps_r != 2 || (H & 1) || (W & 1) || !(act == DASR_ACT_NONE || act == DASR_ACT_RELU || act == DASR_ACT_LRELU02) ||
+        !dasr_conv9_split_supported(H, W, Cin, Cout))
+        return DASR_E_UNSUPPORTED;
+    ConvGeom g{B, H, W, Cin, H, W, Cout, 9, 9, 1, 4, 0};
+    return conv9_split_dgrad_act(g, dconv, dmax, w_hwio, wmax, x_act, dprev, amax, act, stream);
 }
 extern "C" size_t dasr_conv9_wgrad_split2_workspace(int B, int H, int W, int Cin, int Cout) {
     if (B <= 0 || !dasr_conv9_split_supported(H, W, Cin, Cout)) return 0;

@@ -107,6 +107,8 @@ int conv9_split_fwd(const ConvGeom& g, const float* x, const float* xmax, const 
                     float* y, void* stream);
 int conv9_split_dgrad(const ConvGeom& g, const float* dconv, const float* dmax, const float* w, const float* wmax, float* dx,
                       int accumulate, void* stream);
+int conv9_split_dgrad_act(const ConvGeom& g, const float* dconv, const float* dmax, const float* w, const float* wmax,
+                          const float* x_act, float* dprev, float* amax, int act, void* stream);
 size_t conv9_split_wgrad_workspace(const ConvGeom& g);
 int conv9_split_wgrad(const ConvGeom& g, const float* x, const float* xmax, const float* dconv, const float* dmax, float* dw,
                       void* workspace, void* stream);

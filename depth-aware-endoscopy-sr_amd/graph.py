@@ -16,12 +16,18 @@ from . import ops
 from .tape import Tape, Var, accum
 
 
-# dasr_conv2d_dgrad_act (the producer's activation / PixelShuffle backward applied in the consumer's dgrad epilogue)
-# is OFF by default.  Measured on MI355X at the x8 bench shapes it removes the epilogue-backward passes (26 -> 6 ms
-# per 4 steps) but the masked epilogue's extra 4-byte loads and the scattered un-shuffle stores are not hidden
-# under matrix work: the 9x9 dgrad went 3.6 -> 6.2 ms and the 128->128 dgrad 0.82 -> 1.14 ms, a net loss of 4-10 %
-# of the step.  Kept as a tested entry point for shapes where the producer tensor is small.
+# The producer's activation / PixelShuffle backward applied in the consumer's dgrad epilogue, two forms.
+# dasr_conv2d_dgrad_act (exact-fp32 MFMA kernels, any supported geometry) is OFF.  Measured on MI355X at the x8 bench shapes
+# before the split kernels existed, it removed the epilogue-backward passes (26 -> 6 ms per 4 steps) but the masked
+# epilogue's extra 4-byte loads and the scattered un-shuffle stores were not hidden under matrix work: the 9x9 dgrad went
+# 3.6 -> 6.2 ms and the 128->128 dgrad 0.82 -> 1.14 ms, a net loss of 4-10 % of the step.  Kept as a tested entry point for
+# shapes where the producer tensor is small.
 FUSE_DGRAD_ACT = False
+# dasr_conv9_dgrad_act_split2 (csrc/conv9_split.hip) is what runs for the last upscale layer -> 9x9 output convolution pair
+# of the fp32 path: the fp16 x 2 split dgrad holds the whole 2 x 2 block of a channel in one lane, reads the saved activation
+# while it multiplies and stores dprev as 512-byte runs, so d(act) - the largest tensor of the step - is never written or
+# re-read and the k_conv_epilogue_bwd_ps<2> pass of that layer is gone (profiles/c9_dgrad_act_*).
+FUSE_C9_DGRAD_ACT = True
 
 # Run the depth-map branch of the SEANs on a side HIP stream (forward and backward).
 SIDE_STREAM = True
@@ -370,6 +376,7 @@ def conv(tape, x, w, bias=None, *, stride=1, pad=1, transposed=False, act=ops.AC
         residual.uses += 1
     if (act != ops.ACT_NONE or ps_r > 1) and residual is None:
         out.epilogue = (act, ps_r)
+        out.epilogue_split = isinstance(w.split, tuple)
     KH, KW, Cin, Cout = w.data.shape[1:]
     wshape = (KH, KW, Cin, Cout)
     B, H, W_, _ = x.data.shape
@@ -438,6 +445,15 @@ def conv(tape, x, w, bias=None, *, stride=1, pad=1, transposed=False, act=ops.AC
                 # x = PixelShuffle(act(prev conv)) and this conv is its only consumer: write d(prev conv output)
                 x.grad = ops.conv2d_dgrad_act(dconv, w.data, x.data, x.epilogue[0], x.epilogue[1], stride, pad,
                                               transposed)
+                x.grad_is_preact = True
+            elif (_is_c9(w) and FUSE_C9_DGRAD_ACT and x.grad is None and x.uses == 1 and x.epilogue is not None
+                  and ops.conv9_dgrad_act_supported(x.data.shape, Cout, x.epilogue[0], x.epilogue[1])):
+                # x = PixelShuffle(2)(act(upscale3)) and this conv is its only consumer: write d(upscale3's conv output)
+                if dmax is None:
+                    dmax = _amax_t(dconv)
+                x.grad = ops.conv9_dgrad_act_split2(dconv, dmax, w.data, w.split[1], x.data, x.epilogue[0], x.epilogue[1],
+                                                    amax=want_amax(tape, dconv, (B, H // 2, W_ // 2, 4 * Cin))
+                                                    if x.epilogue_split else None)
                 x.grad_is_preact = True
             elif _is_c9(w):
                 if dmax is None:

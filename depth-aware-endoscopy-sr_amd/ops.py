@@ -610,6 +610,23 @@ def conv9_dgrad_split2(dconv, dmax, w, wmax, x_shape, out=None):
     return out
 
 
+def conv9_dgrad_act_supported(x_shape, Cout, act, ps_r):
+    B, H, W, Cin = x_shape
+    return (ps_r == 2 and H % 2 == 0 and W % 2 == 0 and act in (ACT_NONE, ACT_RELU, ACT_LRELU)
+            and conv9_split_supported(H, W, Cin, Cout))
+
+
+def conv9_dgrad_act_split2(dconv, dmax, w, wmax, x_act, act, ps_r, amax=None):
+    """The 9x9 split dgrad with the producer's activation / PixelShuffle(2) backward in its epilogue: x_act [B,H,W,Cin] is the
+    convolution's saved input; returns dprev [B, H/2, W/2, 4 Cin] (max |dprev| left in ``amax`` when given)."""
+    B, H, W, Cin = x_act.shape
+    Cout = dconv.shape[3]
+    dprev = empty((B, H // 2, W // 2, 4 * Cin), dconv)
+    _call("dasr_conv9_dgrad_act_split2", _p(dconv), _p(dmax), _p(w), _p(wmax), _p(x_act), _p(dprev), _p(amax, True),
+          B, H, W, Cin, Cout, act, ps_r)
+    return set_amax(dprev, amax)
+
+
 def conv9_wgrad_split2(x, xmax, dconv, dmax, want_bias=True):
     B, H, W, Cin = x.shape
     Cout = dconv.shape[3]

@@ -12,7 +12,7 @@ from . import ops
 class Var:
     """A device tensor plus its gradient slot."""
     __slots__ = ("data", "grad", "requires_grad", "name", "uses", "epilogue", "grad_is_preact", "event",
-                 "grad_event", "stats", "split", "amax", "pack")
+                 "grad_event", "stats", "split", "amax", "pack", "epilogue_split")
 
     def __init__(self, data, requires_grad=False, name=None):
         self.data = data
@@ -21,7 +21,8 @@ class Var:
         self.name = name
         self.uses = 0                # differentiable consumers recorded during the forward
         self.epilogue = None         # (act, ps_r) when produced by a conv with a fused activation / PixelShuffle
-        self.grad_is_preact = False  # the consumer already applied the epilogue backward (dasr_conv2d_dgrad_act)
+        self.epilogue_split = False  # ... and that conv runs on the fp16 x 2 split kernels (its gradients want max |dconv|)
+        self.grad_is_preact = False  # the consumer already applied the epilogue backward (dasr_conv2d_dgrad_act, dasr_conv9_dgrad_act_split2)
         self.event = None            # HIP event after the producing kernel when it ran on another stream
         self.grad_event = None       # HIP event after the kernel that produced .grad on another stream
         self.stats = None            # (mean, var) per (b, c) when the producing conv computed them in its epilogue

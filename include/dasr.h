@@ -233,6 +233,15 @@ int dasr_conv9_fwd_split2(const float* x, const float* xmax, const float* w_hwio
                           int B, int H, int W, int Cin, int Cout, void* stream);
 int dasr_conv9_dgrad_split2(const float* dconv, const float* dmax, const float* w_hwio, const float* wmax, float* dx,
                             int accumulate, int B, int H, int W, int Cin, int Cout, void* stream);
+/* dasr_conv9_dgrad_split2 with the producer's epilogue backward in its own epilogue (what dasr_conv2d_dgrad_act is to
+ * dasr_conv2d_dgrad): x_act = this convolution's saved input [B,H,W,Cin] = PixelShuffle(2)(act(prev conv)), its only consumer;
+ * dprev [B, H/2, W/2, 4 Cin], dprev[..][4c + 2(y&1) + (x&1)] = dx[y][x][c] * act'(x_act[y][x][c]) - bit for bit what
+ * dasr_conv2d_epilogue_bwd makes of dasr_conv9_dgrad_split2's dx, without dx ever reaching memory.  amax (may be NULL): amax
+ * buffer for max |dprev|.  DASR_E_UNSUPPORTED unless ps_r == 2, H and W are even, act is none / ReLU / LeakyReLU(0.2) and
+ * dasr_conv9_split_supported(H, W, Cin, Cout). */
+int dasr_conv9_dgrad_act_split2(const float* dconv, const float* dmax, const float* w_hwio, const float* wmax, const float* x_act,
+                                float* dprev, float* amax, int B, int H, int W, int Cin, int Cout, int act, int ps_r,
+                                void* stream);
 size_t dasr_conv9_wgrad_split2_workspace(int B, int H, int W, int Cin, int Cout);
 int dasr_conv9_wgrad_split2(const float* x, const float* xmax, const float* dconv, const float* dmax, float* dw_hwio, float* dbias,
                             void* workspace, size_t workspace_bytes, int B, int H, int W, int Cin, int Cout, void* stream);
