@@ -70,8 +70,7 @@ extern "C" int dasr_dynk_fwd(const float* st, const float* A_w, const float* A_b
     size_t n1 = (size_t)B * K * L, n2 = (size_t)B * 18 * K * C;
     DASR_LAUNCH(k_dynk_stp, dim3(dasr_ew_grid(n1)), dim3(256), 0, stream, st, A_w, A_b, stp, K, L, n1);
     (void)n2;
-    if ((L % 2) != 0) return DASR_E_UNSUPPORTED;
-    {
+    {   // (odd L: the `l < L` guards of the operand loads feed the unpaired half of the last K step with zeros)
         int tiles = ((B * K + 31) / 32) * ((18 * C + 31) / 32);
         DASR_LAUNCH(k_dynk_D_mfma, dim3((tiles + 3) / 4), dim3(256), 0, stream, stp, Wg, Wb, D, B, K, L, C);
     }

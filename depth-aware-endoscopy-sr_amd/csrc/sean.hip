@@ -449,20 +449,22 @@ __device__ __forceinline__ void sean_gather(const float* sD, const unsigned char
 // Interior pixels: when the nine region bytes of a pixel's 3x3 neighbourhood are equal (most pixels: depth regions are
 // blobs), gamma1 / beta1 are one row of a per-region table S[s][k] = bias + D[s][0][k] + ... + D[s][8][k] (summed in the
 // gather's own order: bit-identical) - two LDS reads instead of eighteen and no adds.  Taken when EVERY lane of the wave
-// is interior (a vote), so the wave does not run both paths.
+// is interior (a vote), so the wave does not run both paths.  S has a row per region and none for byte K ("no region"):
+// nine "no region" bytes do not count as interior.  They occur outside the image, but also at a pixel INSIDE the image
+// whose whole neighbourhood no mask plane claims (fixed depth range with depth outside it, a constant depth map, a zeroed
+// plane); the gather below gives such a pixel the bare bias from the zero row K of D, as the forward does.
 __device__ __forceinline__ void sean_gather_interior(const float* sD, const float* sS, const unsigned char* sR, int K,
                                                      int K1, int ly, int lx, int cq, float4 bg, float4 bb, float4& g1,
                                                      float4& b1) {
     int k[9];
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) k[tap] = sR[(ly + tap / 3) * (SF_TW + 2) + lx + tap % 3];
-    bool same = true;
+    bool same = k[0] < K;                  // (byte K has no row in S)
 #pragma unroll
     for (int tap = 1; tap < 9; ++tap) same = same && k[tap] == k[0];
-    if (__all(same ? 1 : 0)) {             // (a pixel outside the image sees nine "no region" bytes: clamped, result unused)
-        const int kk = k[0] < K ? k[0] : K - 1;
-        g1 = *(const float4*)(sS + (0 * K + kk) * 64 + 4 * cq);
-        b1 = *(const float4*)(sS + (1 * K + kk) * 64 + 4 * cq);
+    if (__all(same ? 1 : 0)) {
+        g1 = *(const float4*)(sS + (0 * K + k[0]) * 64 + 4 * cq);
+        b1 = *(const float4*)(sS + (1 * K + k[0]) * 64 + 4 * cq);
         return;
     }
     g1 = bg;

@@ -263,7 +263,7 @@ int dasr_instnorm_stats(const float* x, float* mean, float* var, void* workspace
  * style map (normalization.py:27-29,80-85):
  *   stp[b,k,l]       = A_b[k] + sum_j A_w[k,j] * st[b,j,l]
  *   D[b,s,tap,k,c]   = sum_l W_s[c,l,tap] * stp[b,k,l]          s = 0 (gamma), 1 (beta); tap = kh*3+kw
- * W_gamma / W_beta are the module's OIHW tensors [C][L][3][3].
+ * W_gamma / W_beta are the module's OIHW tensors [C][L][3][3].  Any L > 0, odd ones included, forward and backward.
  */
 int dasr_dynk_fwd(const float* st, const float* A_w, const float* A_b, const float* W_gamma, const float* W_beta,
                   float* stp, float* D, int B, int K, int L, int C, void* stream);
@@ -294,7 +294,8 @@ int dasr_dynk_bwd(const float* dD, const float* st, const float* stp, const floa
 /* One byte per pixel from the K mask planes: region[b,y,x] = k if mask[b,k,y,x] == 1 and every other plane is 0,
  * K if all planes are 0; *onehot_flag is set to a non-zero value if ANY pixel is neither (soft / overlapping
  * masks).  The SEAN entry points run a gather kernel when the flag is 0 and the general kernel otherwise; the
- * choice is made on the device, the host never reads the flag. */
+ * choice is made on the device, the host never reads the flag.  A pixel that no plane claims (byte K) adds nothing
+ * to gamma1 / beta1: where a whole 3x3 neighbourhood is unclaimed they are the bare biases, forward and backward. */
 int dasr_mask_compress(const float* mask, unsigned char* region, int* onehot_flag, int B, int K, int H, int W,
                        void* stream);
 int dasr_sean_fwd(const float* t, const float* mean, const float* var, const float* gb2, const float* mask,
