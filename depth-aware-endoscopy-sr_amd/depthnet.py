@@ -269,6 +269,29 @@ class DepthNet(nn.Module):
             out.append(getattr(mod, path[-1]))
         return out
 
+    @torch.no_grad()
+    def infer_nhwc(self, x_nhwc, depthMap, depthMask):
+        """Inference from an NHWC image (``[B,h,w,3]`` float32 RGB, e.g. from ``ops.frame_ingest_u8``): the plan of
+        ``eval()`` + ``no_grad`` ``forward`` - no tape, this module's fold cache - without the two layout passes at its
+        ends.  Returns conv_output's result ``[B,sh,sw,3]`` NHWC BEFORE the clamp to ``[min, max]``; clamped and permuted
+        to NCHW it is ``forward``'s output bit for bit.  Used by ``dasr_amd.video``."""
+        for t, nm in ((x_nhwc, "x_nhwc"), (depthMap, "depthMap"), (depthMask, "depthMask")):
+            if t.dtype != torch.float32 or t.dim() != 4 or t.device != x_nhwc.device or not t.is_contiguous():
+                raise ValueError("DepthNet.infer_nhwc: %s must be a contiguous 4-D float32 tensor on the input's device" % nm)
+        if x_nhwc.shape[3] != self.cfg["in_nc"]:
+            raise ValueError("DepthNet.infer_nhwc: expected [B,h,w,%d], got %s" % (self.cfg["in_nc"], tuple(x_nhwc.shape)))
+        with _device_guard(x_nhwc):
+            params = self._resolve_params()
+            if params and params[0].device != x_nhwc.device:
+                raise ValueError("DepthNet: parameters on %s, input on %s" % (params[0].device, x_nhwc.device))
+            tape = Tape(enabled=False, act_dtype=self._act_dtype(x_nhwc.device))
+            if not hasattr(self, "_fold_cache"):
+                object.__setattr__(self, "_fold_cache", {})
+            tape.fold_cache = self._fold_cache
+            P = {name: Var(p.detach(), False, name) for name, p in zip(self._param_names, params)}
+            return graph.depthnet_infer_nhwc(tape, P, self.cfg, self._consts(x_nhwc.device), x_nhwc, depthMap, depthMask,
+                                             graph.attached_region(depthMask))
+
     def forward(self, input, depthMap, depthMask):
         with _device_guard(input):
             return self._forward(input, depthMap, depthMask)

@@ -893,11 +893,22 @@ def depthnet_forward(tape, P, cfg, consts, inp, depth_map, depth_mask, region=No
             pp.lock.release()
 
 
-def _depthnet_forward(tape, P, cfg, consts, inp, depth_map, depth_mask, region):
+def depthnet_infer_nhwc(tape, P, cfg, consts, x_nhwc, depth_map, depth_mask, region=None):
+    """The inference plan from an NHWC image: ``x_nhwc`` [B,H,W,3] float32 (what dasr_frame_ingest_u8 writes) instead of
+    the reference's NCHW tensor; returns conv_output's NHWC result BEFORE the clamp of sftmd_arch.py:950 (what
+    dasr_frame_emit_u8 reads).  The two layout passes of depthnet_forward are not run; every kernel in between is the
+    same call on the same values.  No tape: for ``eval()`` + ``no_grad`` callers (dasr_amd.video), with the module's
+    fold cache on the tape."""
+    if tape.enabled:
+        raise ValueError("depthnet_infer_nhwc is an inference entry: the tape must be off")
+    return _depthnet_forward(tape, P, cfg, consts, x_nhwc, depth_map, depth_mask, region, nhwc=True).data
+
+
+def _depthnet_forward(tape, P, cfg, consts, inp, depth_map, depth_mask, region, *, nhwc=False):
     plan = block_plan(cfg)
     nb, scale = cfg["nb"], cfg["scale"]
     B = inp.shape[0]
-    x0 = Var(ops.nchw_to_nhwc(inp))
+    x0 = Var(inp if nhwc else ops.nchw_to_nhwc(inp))
     dm = Var(depth_map.reshape(B, depth_map.shape[2], depth_map.shape[3], 1))   # [B,1,h,w] == [B,h,w,1]
     L = ops.ACT_LRELU
     e1, _e5, st = encoder_forward(tape, P, cfg, x0, depth_mask)
@@ -964,6 +975,8 @@ def _depthnet_forward(tape, P, cfg, consts, inp, depth_map, depth_mask, region):
     fea = run_block(nb - 1, fea)
     fea = upscale(tape, P, "upscale3", fea, 3 if scale == 3 else 2, False)
     y = conv(tape, fea, pack(tape, P["conv_output.weight"]), P["conv_output.bias"], pad=4, side_wgrad=True)     # :948
+    if nhwc:
+        return y
     lo, hi = cfg["out_min"], cfg["out_max"]
     out = Var(ops.clamp_to_nchw(y.data, lo, hi), True)                                          # :950
 

@@ -833,3 +833,46 @@ def loss_bwd_soft(sr, hr, mask, dsums, K):
     dsr = torch.empty_like(sr)
     _call("dasr_loss_bwd_soft", _p(sr), _p(hr), _p(mask), _p(dsums), _p(dsr), B, C, h, w, scale, K)
     return dsr
+
+
+# ---- video frames: the uint8 edge of inference (csrc/frame.hip) --------------------------------
+def _pu8(t):
+    return _lib.ptr(t, dtype=torch.uint8)
+
+
+def frame_ingest_u8(frames, swap_rb=True, out=None):
+    """uint8 [B,H,W,C] (HWC, BGR when C == 3 and swap_rb) -> float32 NHWC RGB [B,H,W,C] = frames / 255 (dasr_frame_ingest_u8)."""
+    B, H, W, C = frames.shape
+    if out is None:
+        out = torch.empty((B, H, W, C), dtype=torch.float32, device=frames.device)
+    assert tuple(out.shape) == (B, H, W, C)
+    drop_amax(out)
+    _call("dasr_frame_ingest_u8", _pu8(frames), _p(out), B, H, W, C, int(bool(swap_rb)))
+    return out
+
+
+def frame_emit_u8(y, net_lo, net_hi, min_max=(0, 1), swap_rb=True, out=None):
+    """float32 NHWC [B,H,W,C] before the output clamp -> uint8 [B,H,W,C] (BGR when C == 3 and swap_rb): clamp to the net's
+    range, then tensor2img's clamp / rescale / round(x * 255) (dasr_frame_emit_u8)."""
+    B, H, W, C = y.shape
+    if out is None:
+        out = torch.empty((B, H, W, C), dtype=torch.uint8, device=y.device)
+    assert tuple(out.shape) == (B, H, W, C)
+    _call("dasr_frame_emit_u8", _p(y), _pu8(out), B, H, W, C, float(net_lo), float(net_hi), float(min_max[0]),
+          float(min_max[1]), int(bool(swap_rb)))
+    return out
+
+
+def frame_ssd_u8(a, b, crop=0, out=None):
+    """Exact sum of squared differences per frame of two uint8 [B,H,W,C] batches inside a ``crop``-pixel border, as int64
+    [B] on the device (dasr_frame_ssd_u8 writes unsigned 64-bit sums; they stay below 2^63 for any image that fits memory)."""
+    assert a.shape == b.shape
+    B, H, W, C = a.shape
+    if out is None:
+        out = torch.empty((B,), dtype=torch.int64, device=a.device)
+    assert out.numel() == B
+    nbytes = int(_lib.get().dasr_frame_ssd_u8_workspace(B, H, W, C, int(crop)))
+    ws = torch.empty((max(nbytes, 8) // 8,), dtype=torch.int64, device=a.device)
+    _call("dasr_frame_ssd_u8", _pu8(a), _pu8(b), _lib.ptr(out, dtype=torch.int64), _lib.ptr(ws, dtype=torch.int64), nbytes,
+          B, H, W, C, int(crop))
+    return out

@@ -88,3 +88,52 @@ def validate(net, frames, scale):
         psnr_sum += calculate_psnr(sr_img[c:-c, c:-c, :] * 255, gt_img[c:-c, c:-c, :] * 255)
         n += 1
     return psnr_sum / max(n, 1), ssim_sum / max(n, 1), n
+
+
+def validate_u8(net, frames, scale, num_masks=10, fixed_range=False, use_graph=False):
+    """The loop of ``validate()`` for a video source: ``frames`` yields ``(LQ, GT, Depth)`` with ``LQ`` a ``uint8``
+    ``[1,h,w,3]`` (or ``[h,w,3]``) BGR frame as ``cv2`` reads it, ``GT`` the ``[1,3,sh,sw]`` float tensor and ``Depth``
+    ``[1,1,h,w]``; a fourth item (the reference loader's mask list) is ignored, the masks are binned on the device.
+    SR comes from ``video.FrameUpscaler``; GT is quantised by the same kernel's ``tensor2img`` half; PSNR is
+    ``20 log10(255 / sqrt(ssd / n))`` from the exact integer sum of squared differences of the two uint8 images with a
+    ``scale``-pixel border cropped (``dasr_frame_ssd_u8``; ``inf`` at ``ssd == 0``); SSIM is ``dasr_ssim`` of the [0,1]
+    tensors as in ``validate()``.  Nothing is read back per frame: the sums stay on the device and come to the host in
+    one transfer at the end.  Returns (avg_psnr, avg_ssim, n)."""
+    from . import ops
+    from .video import FrameUpscaler
+    up = FrameUpscaler(net, num_masks=num_masks, fixed_range=fixed_range, use_graph=use_graph, min_max=(0, 1))
+    dev = up.device
+    CHUNK = 256
+    chunks, counts = [], []              # int64 [2*CHUNK] each: ssd in the first half, ssim (float32 bits) in the second
+
+    def view(i):
+        if i // CHUNK >= len(chunks):
+            chunks.append(torch.zeros((2 * CHUNK,), dtype=torch.int64, device=dev))
+        buf, j = chunks[i // CHUNK], i % CHUNK
+        return buf[j:j + 1], buf[CHUNK:].view(torch.float32)[j:j + 1]
+
+    inf = float("inf")
+    with torch.no_grad():
+        for i, item in enumerate(frames):
+            lq, gt, depth = item[0], item[1], item[2]
+            lq = lq if torch.is_tensor(lq) else torch.from_numpy(np.ascontiguousarray(lq))
+            sr_u8, y = up.upscale_device(lq[None] if lq.dim() == 3 else lq, depth)     # on the device, nothing waited for
+            gt = gt[:1].to(dev).float().contiguous()
+            ssd_out, ssim_out = view(i)
+            sr = ops.clamp_to_nchw(y[:1].contiguous(), net.min, net.max)
+            ops.copy_(ssim_out, ssim(sr, gt, size_average=False))
+            gt_u8 = ops.frame_emit_u8(ops.nchw_to_nhwc(gt), -inf, inf, (0, 1), swap_rb=True)
+            _, H, W, C = gt_u8.shape
+            ops.frame_ssd_u8(sr_u8[:1].contiguous(), gt_u8, crop=scale, out=ssd_out)
+            counts.append((H - 2 * scale) * (W - 2 * scale) * C)
+    n = len(counts)
+    if n == 0:
+        return 0.0, 0.0, 0
+    host = (chunks[0] if len(chunks) == 1 else torch.cat(chunks)).cpu()          # the one read-back
+    psnr_sum = ssim_sum = 0.0
+    for i, cnt in enumerate(counts):
+        buf, j = host[2 * CHUNK * (i // CHUNK):2 * CHUNK * (i // CHUNK + 1)], i % CHUNK
+        ssd = int(buf[j])
+        psnr_sum += inf if ssd == 0 else 20 * math.log10(255.0 / math.sqrt(ssd / cnt))
+        ssim_sum += float(buf[CHUNK:].view(torch.float32)[j])
+    return psnr_sum / n, ssim_sum / n, n

@@ -479,6 +479,38 @@ size_t dasr_ssim_workspace(int B, int C, int H, int W);
 int dasr_ssim(const float* img1, const float* img2, const float* window11, float* out_per_sample, void* workspace,
               size_t workspace_bytes, int B, int C, int H, int W, void* stream);
 
+/* ---- video frames: the uint8 edge of inference (csrc/frame.hip) ----------------------------------------------------
+ * A camera frame is uint8 HWC (BGR as cv2 delivers it); the network is NHWC inside.  These three keep the host out of the
+ * per-frame path: one byte per sample crosses PCIe in each direction and no layout pass runs on either side.
+ *
+ * dasr_frame_ingest_u8: frames uint8 [B,H,W,C] -> x_nhwc float [B,H,W,C] = frames / 255 (IEEE division, bit-identical
+ * to `img.astype(np.float32) / 255.`); swap_rb != 0 with C == 3 reverses the channel order (BGR -> RGB).  Replaces
+ * read_img's `astype(np.float32) / 255.` (codes/data/util.py:78) and img2tensor (codes/utils/util.py:596-605: the same
+ * division, `[:, :, [2, 1, 0]]`, `transpose(2, 0, 1)`) together with dasr_nchw_to_nhwc. */
+int dasr_frame_ingest_u8(const unsigned char* frames, float* x_nhwc, int B, int H, int W, int C, int swap_rb,
+                         void* stream);
+/* dasr_frame_emit_u8: y_nhwc float [B,H,W,C] (conv_output's result BEFORE the clamp) -> frames uint8 [B,H,W,C]:
+ *   v = clamp(y, net_lo, net_hi)                         torch.clamp(out, min, max), sftmd_arch.py:950
+ *   v = clamp(v, mm_lo, mm_hi); v = (v - mm_lo) / (mm_hi - mm_lo); u = rint(v * 255)      tensor2img, utils/util.py:572-590
+ * in fp32, ties to even (numpy's round), bit-identical to tensor2img(dasr_clamp_to_nchw(y)[b], min_max=(mm_lo, mm_hi)) for
+ * every finite y (NaN: unspecified).  mm_lo / mm_hi are doubles because tensor2img forms `max - min` in Python doubles
+ * before torch rounds it to float32.  swap_rb != 0 with C == 3 writes BGR (tensor2img's `[[2, 1, 0], :, :]`).
+ * C must be 1 or 3 (DASR_E_UNSUPPORTED otherwise); mm_hi > mm_lo.
+ * Alignment (ingest and emit): any addresses are accepted, but the wide path (12 bytes / three 16-byte accesses per lane)
+ * needs an element offset at which the uint8 address is a multiple of 4 AND the float address a multiple of 16; pass a
+ * 4-byte-aligned uint8 buffer and a 16-byte-aligned float buffer (any hipMalloc result) to get it - with incompatible
+ * residues the whole batch goes one element per lane, correct but several times slower. */
+int dasr_frame_emit_u8(const float* y_nhwc, unsigned char* frames, int B, int H, int W, int C, float net_lo, float net_hi,
+                       double mm_lo, double mm_hi, int swap_rb, void* stream);
+/* dasr_frame_ssd_u8: ssd[b] = sum over rows / columns crop .. H-1-crop / W-1-crop and all C channels of (a - b)^2, exact
+ * (unsigned 64-bit), for two uint8 [B,H,W,C] image batches: the `mse` of calculate_psnr (utils/util.py:646-653) times the
+ * sample count, on the cropped uint8 images codes/train.py:245-262 hands it.  PSNR = 20 log10(255 / sqrt(ssd / n)),
+ * n = (H - 2 crop)(W - 2 crop) C.  2 crop >= H or 2 crop >= W: DASR_E_UNSUPPORTED.
+ * workspace: dasr_frame_ssd_u8_workspace() bytes (one 64-bit partial per workgroup; no atomics). */
+size_t dasr_frame_ssd_u8_workspace(int B, int H, int W, int C, int crop);
+int dasr_frame_ssd_u8(const unsigned char* a, const unsigned char* b, unsigned long long* ssd, void* workspace,
+                      size_t workspace_bytes, int B, int H, int W, int C, int crop, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
