@@ -8,5 +8,9 @@ through the C ABI declared in ``include/dasr.h``.
 
 Importing the package does not load the HIP library; the first kernel call does,
 and raises if ``libdasr_hip.so`` has not been built (``__graft_entry__.build()``).
+
+Sub-modules beside the generator: ``harness`` (training step), ``validate``, ``prep`` (depth masks on the device),
+``video`` (uint8 video inference), ``data`` (training batches from uint8 HR frames: ``data.BatchMaker``).
 """
 __version__ = "0.1.0"
+__all__ = ["data", "depthnet", "graph", "harness", "networks", "ops", "prep", "synth", "validate", "video"]

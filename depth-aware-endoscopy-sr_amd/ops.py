@@ -703,14 +703,19 @@ def mask_compress(mask):
     return region, flag
 
 
-def depth_to_masks(depth, num_masks=10, fixed_edges=None, want_planes=True):
+def depth_to_masks(depth, num_masks=10, fixed_edges=None, want_planes=True, out=None):
     """Device getDepthMask (dasr_depth_to_masks): depth [B,1,h,w] or [B,h,w] -> (planes [B,K,h,w] float or None,
-    region bytes [B,h,w]).  fixed_edges: None (per-sample min/max range) or K+1 float32 device values."""
+    region bytes [B,h,w]).  fixed_edges: None (per-sample min/max range) or K+1 float32 device values.  ``out``:
+    ``(planes, region)`` buffers of those shapes to write into instead of new ones."""
     h, w = depth.shape[-2:]
     B = depth.numel() // (h * w)
     d = depth.contiguous()
-    planes = torch.empty((B, num_masks, h, w), dtype=torch.float32, device=d.device) if want_planes else None
-    region = torch.empty((B, h, w), dtype=torch.uint8, device=d.device)
+    if out is not None:
+        planes, region = out
+        assert tuple(region.shape) == (B, h, w) and (planes is None or tuple(planes.shape) == (B, num_masks, h, w))
+    else:
+        planes = torch.empty((B, num_masks, h, w), dtype=torch.float32, device=d.device) if want_planes else None
+        region = torch.empty((B, h, w), dtype=torch.uint8, device=d.device)
     nbytes = int(_lib.get().dasr_depth_to_masks_workspace(B, h * w))
     ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=d.device)
     _call("dasr_depth_to_masks", _p(d), _p(fixed_edges, True) if fixed_edges is not None else None,
@@ -875,4 +880,98 @@ def frame_ssd_u8(a, b, crop=0, out=None):
     ws = torch.empty((max(nbytes, 8) // 8,), dtype=torch.int64, device=a.device)
     _call("dasr_frame_ssd_u8", _pu8(a), _pu8(b), _lib.ptr(out, dtype=torch.int64), _lib.ptr(ws, dtype=torch.int64), nbytes,
           B, H, W, C, int(crop))
+    return out
+
+
+# ---- training batches from uint8 HR frames (csrc/batch.hip) --------------------------------------------------------
+def _pi32(t, allow_none=False):
+    return _lib.ptr(t, allow_none, dtype=torch.int32)
+
+
+def _batch_tables(B, origins, flags, device):
+    """Pointers of the per-sample device tables (None: no crop offset / no augmentation) after a shape and dtype check."""
+    if origins is not None and (origins.dtype != torch.int32 or tuple(origins.shape) != (B, 2)):
+        raise TypeError("dasr_amd: origins must be int32 [B,2], got %s %s" % (origins.dtype, tuple(origins.shape)))
+    if flags is not None and (flags.dtype != torch.uint8 or tuple(flags.shape) != (B,)):
+        raise TypeError("dasr_amd: flags must be uint8 [B], got %s %s" % (flags.dtype, tuple(flags.shape)))
+    return _pi32(origins, True), (_pu8(flags) if flags is not None else None)
+
+
+def _batch_out(out, shape, dtype, like):
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=like.device)
+    if tuple(out.shape) != tuple(shape):
+        raise ValueError("dasr_amd: out has shape %s, expected %s" % (tuple(out.shape), tuple(shape)))
+    drop_amax(out)
+    return out
+
+
+def _batch_check(name, rc):
+    """Shape refusals of the batch entry points are the caller's error: ValueError, like the Python-side checks."""
+    if rc in (-2, -3):
+        msg = _lib.get().dasr_error_string(rc)
+        raise ValueError("dasr_amd: %s refused: %s (code %d)" % (name, msg.decode() if msg else "?", rc))
+    _lib.check(rc, name)
+
+
+def batch_lr_u8(frames, scale, tables, window=None, origins=None, flags=None, allow_transpose=False, out=None):
+    """uint8 [B,H,W,3] HWC BGR -> float32 [B,3,ch,cw] NCHW RGB: the reference's LR image ``imresize_np(frames / 255,
+    1 / scale, True)``, its window ``(ch, cw)`` at the per-sample ``origins``, augmented by the per-sample ``flags``
+    (dasr_batch_lr_u8).  ``tables`` = (wh, ih, ww, iw) device tensors from ``data.resize_tables``; ``window`` None: the
+    whole LR image; ``origins`` int32 [B,2] / ``flags`` uint8 [B] on the device, or None."""
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+        raise TypeError("dasr_amd: frames must be uint8 [B,H,W,3], got %s %s" % (frames.dtype, tuple(frames.shape)))
+    B, H, W, _ = frames.shape
+    s = int(scale)
+    if s <= 0 or H % s or W % s:
+        raise ValueError("dasr_amd: frame size %dx%d is not a multiple of the scale %d" % (H, W, s))
+    wh, ih, ww, iw = tables
+    if tuple(wh.shape) != (H // s, 4 * s) or tuple(ww.shape) != (W // s, 4 * s) or ih.numel() != H // s or iw.numel() != W // s:
+        raise ValueError("dasr_amd: resize tables do not belong to %dx%d frames at scale %d" % (H, W, s))
+    ch, cw = (H // s, W // s) if window is None else (int(window[0]), int(window[1]))
+    po, pf = _batch_tables(B, origins, flags, frames.device)
+    out = _batch_out(out, (B, 3, ch, cw), torch.float32, frames)
+    rc = _lib.get().dasr_batch_lr_u8(_pu8(frames), _p(out), _p(wh), _pi32(ih), _p(ww), _pi32(iw), po, pf, B, H, W, s, ch, cw,
+                                     int(bool(allow_transpose)), _lib.stream())
+    _batch_check("dasr_batch_lr_u8", rc)
+    return out
+
+
+def batch_gt_u8(frames, scale, window=None, origins=None, flags=None, allow_transpose=False, out=None):
+    """uint8 [B,H,W,3] HWC BGR -> float32 [B,3,s*ch,s*cw] NCHW RGB GT: ``frames / 255`` (the values of
+    ``frame_ingest_u8``) of the HR window that belongs to the LR ``window`` at ``origins``, augmented (dasr_batch_gt_u8)."""
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+        raise TypeError("dasr_amd: frames must be uint8 [B,H,W,3], got %s %s" % (frames.dtype, tuple(frames.shape)))
+    B, H, W, _ = frames.shape
+    s = int(scale)
+    if s <= 0 or H % s or W % s:
+        raise ValueError("dasr_amd: frame size %dx%d is not a multiple of the scale %d" % (H, W, s))
+    ch, cw = (H // s, W // s) if window is None else (int(window[0]), int(window[1]))
+    po, pf = _batch_tables(B, origins, flags, frames.device)
+    out = _batch_out(out, (B, 3, s * ch, s * cw), torch.float32, frames)
+    rc = _lib.get().dasr_batch_gt_u8(_pu8(frames), _p(out), po, pf, B, H, W, s, ch, cw, int(bool(allow_transpose)),
+                                     _lib.stream())
+    _batch_check("dasr_batch_gt_u8", rc)
+    return out
+
+
+def batch_plane(x, window=None, origins=None, flags=None, allow_transpose=False, out=None):
+    """float32 or uint8 [B,C,h,w] -> [B,C,ch,cw]: the window of every plane, augmented (dasr_batch_plane_f32 / _u8): the
+    depth map, the mask planes, the region bytes ([B,h,w] uint8 is taken as C = 1 and returned as [B,ch,cw])."""
+    if x.dtype not in (torch.float32, torch.uint8):
+        raise TypeError("dasr_amd: batch_plane takes float32 or uint8, got %s" % x.dtype)
+    if x.dim() not in (3, 4):
+        raise TypeError("dasr_amd: batch_plane takes [B,C,h,w] or [B,h,w], got %s" % (tuple(x.shape),))
+    B, h, w = x.shape[0], x.shape[-2], x.shape[-1]
+    C = x.shape[1] if x.dim() == 4 else 1
+    ch, cw = (h, w) if window is None else (int(window[0]), int(window[1]))
+    po, pf = _batch_tables(B, origins, flags, x.device)
+    out = _batch_out(out, (B, C, ch, cw) if x.dim() == 4 else (B, ch, cw), x.dtype, x)
+    if x.dtype == torch.float32:
+        rc = _lib.get().dasr_batch_plane_f32(_p(x), _p(out), po, pf, B, C, h, w, ch, cw, int(bool(allow_transpose)),
+                                             _lib.stream())
+    else:
+        rc = _lib.get().dasr_batch_plane_u8(_pu8(x), _pu8(out), po, pf, B, C, h, w, ch, cw, int(bool(allow_transpose)),
+                                            _lib.stream())
+    _batch_check("dasr_batch_plane", rc)
     return out

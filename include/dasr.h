@@ -511,6 +511,39 @@ size_t dasr_frame_ssd_u8_workspace(int B, int H, int W, int C, int crop);
 int dasr_frame_ssd_u8(const unsigned char* a, const unsigned char* b, unsigned long long* ssd, void* workspace,
                       size_t workspace_bytes, int B, int H, int W, int C, int crop, void* stream);
 
+/* ---- training batches from uint8 HR frames (csrc/batch.hip) --------------------------------------------------------
+ * The image half of the reference's training loader (codes/data/LQGTker_Depth_dataset.py:145-199) on the device: the
+ * uint8 HR frames cross PCIe, the LR image, the float GT, the augmentation and the NCHW RGB packing happen here.
+ * Shared arguments: frames uint8 [B,H,W,3] HWC BGR; s the scale; (ch, cw) the size of the LR window (ch <= H/s,
+ * cw <= W/s; the full frame: ch = H/s, cw = W/s); origins DEVICE int32 [B,2] = (oy, ox) of each sample's window in LR
+ * pixels (NULL: all zero; values outside the frame are clamped into it); flags DEVICE uint8 [B], bit 0 hflip, bit 1
+ * vflip, bit 2 transpose, applied in the order of augment (codes/data/util.py:101-118): img[:, ::-1], img[::-1],
+ * transpose(1, 0, 2) (NULL: none).  allow_transpose != 0 says the flags may carry bit 2 and requires ch == cw
+ * (DASR_E_SHAPE otherwise: a batch has one shape); with allow_transpose == 0 bit 2 is ignored.
+ *
+ * dasr_batch_lr_u8: lr float [B,3,ch,cw] NCHW RGB = the window of imresize_np(frames / 255, 1/s, antialiasing=True)
+ * (codes/data/util.py:258-458: cubic, calculate_weights_indices, imresize_np; the division is read_img's,
+ * codes/data/util.py:71-84), augmented.  Separable, H pass first, its result rounded to fp32; 4s taps per output;
+ * symmetric edge-including reflection, applied by the kernel; not clamped, not rounded.  wh / ww: DEVICE float
+ * [H/s, 4s] / [W/s, 4s] tap weights, ih / iw: DEVICE int32 [H/s] / [W/s] 0-based index of each output's first tap (may be
+ * negative).  s in {2, 3, 4, 8} (DASR_E_UNSUPPORTED otherwise); H % s == 0, W % s == 0 and H, W >= floor(0.5 + 1.5 s),
+ * the reflection length, below which the reference raises (DASR_E_SHAPE).  Each output is one fmaf chain in tap order:
+ * its bits depend on neither the window, the batch nor the launch geometry. */
+int dasr_batch_lr_u8(const unsigned char* frames, float* lr, const float* wh, const int* ih, const float* ww,
+                     const int* iw, const int* origins, const unsigned char* flags, int B, int H, int W, int s, int ch,
+                     int cw, int allow_transpose, void* stream);
+/* dasr_batch_gt_u8: gt float [B,3,s*ch,s*cw] NCHW RGB = frames / 255 (IEEE division, the values of dasr_frame_ingest_u8;
+ * read_img, codes/data/util.py:71-84) of the HR window at s * (oy, ox), augmented (codes/data/util.py:101-118) and packed
+ * as LQGTker_Depth_dataset.py:186-193 does.  Any s > 0 with H % s == 0 and W % s == 0. */
+int dasr_batch_gt_u8(const unsigned char* frames, float* gt, const int* origins, const unsigned char* flags, int B, int H,
+                     int W, int s, int ch, int cw, int allow_transpose, void* stream);
+/* dasr_batch_plane_f32 / _u8: in [B,C,h,w] -> out [B,C,ch,cw]: the window (oy, ox, ch, cw) of every plane, augmented
+ * (codes/data/util.py:101-118 on the depth map and the mask list, LQGTker_Depth_dataset.py:176-193).  B * C <= 65535. */
+int dasr_batch_plane_f32(const float* in, float* out, const int* origins, const unsigned char* flags, int B, int C, int h,
+                         int w, int ch, int cw, int allow_transpose, void* stream);
+int dasr_batch_plane_u8(const unsigned char* in, unsigned char* out, const int* origins, const unsigned char* flags, int B,
+                        int C, int h, int w, int ch, int cw, int allow_transpose, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
