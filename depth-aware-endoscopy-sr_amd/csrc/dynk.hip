@@ -41,8 +41,11 @@ __global__ void __launch_bounds__(256) k_dynk_D_mfma(const float* __restrict__ s
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
     // sixteen K steps per trip: 32 operand loads in flight before the first MFMA (one load pair per MFMA was a chain of
-    // L/2 = 128 L2 round trips: 77 us for 6 MFLOP)
-    for (int l0 = lh; l0 < L; l0 += 32) {
+    // L/2 = 128 L2 round trips: 77 us for 6 MFLOP).  The trip count is the same for every lane of the wave (a block base,
+    // the lane half added inside): an MFMA needs the whole wave, and a loop started at `lh` gave lane half 0 one more trip
+    // than lane half 1 whenever L = 32 n + 1.  The `l < L` guards feed the steps past the end with zeros.
+    for (int lb = 0; lb < L; lb += 32) {
+        const int l0 = lb + lh;
         float av[16], bv[16];
 #pragma unroll
         for (int u = 0; u < 16; ++u) {
@@ -70,7 +73,8 @@ extern "C" int dasr_dynk_fwd(const float* st, const float* A_w, const float* A_b
     size_t n1 = (size_t)B * K * L, n2 = (size_t)B * 18 * K * C;
     DASR_LAUNCH(k_dynk_stp, dim3(dasr_ew_grid(n1)), dim3(256), 0, stream, st, A_w, A_b, stp, K, L, n1);
     (void)n2;
-    {   // (odd L: the `l < L` guards of the operand loads feed the unpaired half of the last K step with zeros)
+    {   // (any L: every lane makes ceil(L / 32) trips of sixteen K steps; the `l < L` guards of the operand loads feed the
+        // steps past the end - the unpaired half of the last K step of an odd L among them - with zeros)
         int tiles = ((B * K + 31) / 32) * ((18 * C + 31) / 32);
         DASR_LAUNCH(k_dynk_D_mfma, dim3((tiles + 3) / 4), dim3(256), 0, stream, stp, Wg, Wb, D, B, K, L, C);
     }
@@ -97,7 +101,8 @@ __global__ void __launch_bounds__(256) k_dynk_dW_mfma(const float* __restrict__ 
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    for (int kk0 = lh; kk0 < KK; kk0 += 32) {          // sixteen K steps per trip, loads first (see k_dynk_D_mfma)
+    for (int kb = 0; kb < KK; kb += 32) {              // sixteen K steps per trip, loads first; a wave-uniform trip count
+        const int kk0 = kb + lh;                       // (see k_dynk_D_mfma)
         float av[16], bv[16];
 #pragma unroll
         for (int u = 0; u < 16; ++u) {
@@ -149,7 +154,8 @@ __global__ void __launch_bounds__(64 * DSTP_WAVES) k_dynk_dstp_mfma(const float*
         const float* ap = dD + (((size_t)b * 18 + st0) * K + k) * C;                 // + q * K * C + c
         const float* bp = (st0 >= 9 ? Wb : Wg) + (size_t)(nv ? n : 0) * 9 + st0 % 9; // + c * L * 9 + q
         const int KKW = QW * C;
-        for (int kk0 = lh; kk0 < KKW; kk0 += 32) { // sixteen K steps per trip, all 32 loads issued before the first MFMA
+        for (int kb = 0; kb < KKW; kb += 32) {     // sixteen K steps per trip, all 32 loads issued before the first MFMA;
+            const int kk0 = kb + lh;               // a wave-uniform trip count (see k_dynk_D_mfma)
             float av[16], bv[16];
 #pragma unroll
             for (int u = 0; u < 16; ++u) {
