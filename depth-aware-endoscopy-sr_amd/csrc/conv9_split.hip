@@ -10,9 +10,10 @@
 //   wgrad:    dW[kh][k'][ci] = sum_q x[q][ci] * E[q.y-kh+4][q.x][k']                         M = ci, N = 27, K = pixels
 // with k' = Cout*(8-kw) + co and E[row][px][k'] = the 27 consecutive values of the 3-channel dy row starting at pixel px-4.
 // Everything that is an MFMA operand lives in LDS as TWO fp16 images (value and what the first rounding left), so tiles are
-// half the size of the bf16 kernels': the forward walks 16-channel chunks of an 8 x 56 pixel tile, the wgrad 8 x 32 tiles, the
-// dgrad 8 x 16 tiles.  All three kernels are persistent (forward / wgrad: one 512-thread workgroup per CU, dgrad: two of 256;
-// kernel images staged once) and hold the next tile's global loads in registers while the current one is multiplied.
+// half the size of the bf16 kernels': the forward walks 16-channel chunks of an 8 x 24 pixel tile (its first form: 8 x 56), the
+// wgrad 8 x 32 tiles, the dgrad 8 x 16 tiles.  All three kernels are persistent (forward and dgrad: two 256-thread workgroups
+// per CU whose phases overlap, wgrad: one of 512; kernel images staged once) and hold the next tile's global loads in
+// registers while the current one is multiplied.
 #include "bf16.h"
 #include "conv_kernels.h"
 
@@ -88,7 +89,8 @@ __device__ __forceinline__ f32x16 s9_mma(const h16x8& a0, const h16x8& a1, const
     return c;
 }
 
-// ------------------------------------------------------------------------------------------ forward
+// ------------------------------------------------------------------------------------------ forward, first form
+// (dasr_set_conv_bf16_impl(+ 8192), and every Cin other than 32: A/B runs and the equality test of the form below)
 // 512 threads, tile = 8 rows x 56 columns of y (input tile 16 x 64 pixels), wave w owns tile row w (two 32-pixel M-tiles).
 // K loop: 16-channel chunks; per chunk 9 kh x 2 M-tiles x 3 products = 54 MFMAs per wave.  LDS: two input images
 // [16*64 px][24] fp16 (48-byte pixel stride: conflict-free ds_read_b128), the kernel [Cin/16][9 kh][32 n][24] x 2, the P
@@ -96,7 +98,7 @@ __device__ __forceinline__ f32x16 s9_mma(const h16x8& a0, const h16x8& a1, const
 #define S9F_TQ 64
 #define S9F_ST 24
 #define S9F_PST 28
-__global__ void __launch_bounds__(512) k_conv9_fwd_split(Conv9SplitArgs a) {
+__global__ void __launch_bounds__(512) k_conv9_fwd_split_1wg(Conv9SplitArgs a) {
     DASR_DYN_SMEM(smem);
     constexpr int NPX = (S9_TH + 8) * S9F_TQ;                      // 1024 staged pixels
     h16_t* sIn0 = (h16_t*)smem;                                    // [NPX][S9F_ST]
@@ -240,44 +242,197 @@ __global__ void __launch_bounds__(512) k_conv9_fwd_split(Conv9SplitArgs a) {
     }
 }
 
-// ------------------------------------------------------------------------------------------ the E image (dgrad / wgrad)
-// tile = 8 rows x 32 columns.  sDy: fp32 dy tile, rows y0-4 .. y0+11, columns x0-4 .. x0+35, Cout channels interleaved (zero
-// outside the image).  E[row][px][k'] (two fp16 images, EST elements per pixel) = sd * sDy[row][Cout*px + k'], 0 for k' >= 9 Cout.
-#define S9_TQ 32
-#define S9_DYW ((S9_TQ + 8) * 3 + 8)      // fp32 dy tile row stride: 40 px * 3 ch + pad = 128
-template <int EST>
-__device__ __forceinline__ void s9_build_E(const Conv9SplitArgs& a, const float* sDy, h16_t* sE0, h16_t* sE1, float sd, int tid) {
-    const int KK = 9 * a.Cout;
-    for (int pc = tid; pc < (S9_TH + 8) * S9_TQ * 4; pc += 512) {         // 16-byte pieces: (row, px, 8 k')
-        const int p8 = pc & 3, px = (pc >> 2) % S9_TQ, row = pc / (4 * S9_TQ);
-        const float* src = sDy + row * S9_DYW + a.Cout * px + 8 * p8;
-        h16x8 o0, o1;
+// ------------------------------------------------------------------------------------------ forward (Cin = 32)
+// 256 threads, TWO workgroups per CU (68.1 KB of LDS each) whose phases overlap: while one stages a chunk, writes its P image
+// or does the shift-add, the other multiplies.  tile = 8 rows x 24 columns of y (input tile 16 x 32 pixels); wave w owns tile
+// rows 2w, 2w+1 as two 32-pixel M-tiles.  Per 16-channel chunk and kh the two M-tiles take input rows 2w+kh and 2w+kh+1, so a
+// row's fragment serves (kh, upper tile row) and (kh-1, lower): 10 A and 9 B fragment pairs per chunk for 54 MFMAs, read one
+// kh ahead.  The order of the products of every output element is the first form's (chunk, kh, s9_mma's three, then the
+// shift-add over kw from 0, then fmaf(v, inv, bias)): the two forms give the same bits.
+// LDS: the input chunk as 2 x [16*32 px][16 ch] fp16 (32-byte pixel stride, the 16-byte piece index XORed with (px >> 3) & 1),
+// the kernel as 2 x [9 kh][32 n][32 ci] (64-byte stride, piece index XORed with (n >> 2) & 3, as the dgrad's Wd): each 16-lane
+// group of a ds_read_b128 meets every 16-byte slot of a bank row once.  The P image [8][32][28] fp32 aliases the input chunk.
+// What does not depend on the tile - the staged pieces' pixel and LDS address, the shift-add's output -> (row, column, co)
+// map with its divisions by Cout - is computed once per thread.  Loads and stores go through range-checked descriptors (out
+// of the image and ragged tiles: DASR_OOB), every barrier is LDS-only: a tile's stores drain under the next tile's work and
+// the next chunk's loads stay in flight across the MFMA phase.
+#define S9G_TQ 32                      // staged columns
+#define S9G_TWO (S9G_TQ - 8)           // output columns of a tile
+#define S9G_PST 28
+constexpr int S9G_NPX = (S9_TH + 8) * S9G_TQ;                      // 512 staged pixels
+constexpr size_t S9G_LDS = sizeof(h16_t) * (size_t)(2 * S9G_NPX * 16 + 2 * 9 * 32 * 32) + 128;
+static_assert(2 * S9G_LDS <= 160 * 1024, "two workgroups per CU");
+static_assert(sizeof(float) * S9_TH * S9G_TQ * S9G_PST <= sizeof(h16_t) * 2 * S9G_NPX * 16, "the P image fits the input chunk");
+constexpr int S9G_NOUT = (S9_TH * S9G_TWO * 3 + 255) / 256;        // shift-add trips of 256 threads (Cout <= 3)
+__global__ void __launch_bounds__(256, 2) k_conv9_fwd_split(Conv9SplitArgs a) {
+    DASR_DYN_SMEM(smem);
+    h16_t* sIn0 = (h16_t*)smem;                                    // [512 px][16], pieces swizzled
+    h16_t* sIn1 = sIn0 + S9G_NPX * 16;
+    h16_t* sW0 = sIn1 + S9G_NPX * 16;                              // [9 kh][32 n][32 ci], pieces swizzled
+    h16_t* sW1 = sW0 + 9 * 32 * 32;
+    float* s_red = (float*)(sW1 + 9 * 32 * 32);                    // [32]
+    const int tid = threadIdx.x, lane = tid & 63, wv = DASR_UNIFORM((int)(tid >> 6)), li = lane & 31, lh = lane >> 5;
+    const int tiles_x = (a.W + S9G_TWO - 1) / S9G_TWO, tiles_y = (a.H + S9_TH - 1) / S9_TH;
+    const int total = tiles_x * tiles_y * a.B;
+    const int NN = 9 * a.Cout;   // <= 27
+    int kx, kw_;
+    s9_scales(a.xmax, a.wmax, s_red, kx, kw_);
+    const float sx = s9_pow2(kx), sw = s9_pow2(kw_), inv = s9_pow2(-(kx + kw_));
+#pragma unroll 1
+    for (int h = 0; h < 2; ++h) {                                  // sW[kh][n = kw*Cout+co][ci] (zero rows for n >= 9*Cout), once
+        float wq[18];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            h16_t h0, h1;
-            s9_split(8 * p8 + j < KK ? src[j] : 0.f, sd, h0, h1);
-            o0[j] = h0; o1[j] = h1;
+        for (int u = 0; u < 18; ++u) {
+            const int e = tid + 256 * (18 * h + u), ci = e & 31, n = (e >> 5) & 31, kh = e >> 10;
+            const int nn = n < NN ? n : 0, kw = nn / a.Cout, co = nn % a.Cout;
+            const float v = a.w[(((size_t)kh * 9 + kw) * 32 + ci) * a.Cout + co];
+            wq[u] = n < NN ? v : 0.f;
         }
-        *(h16x8*)(sE0 + (row * S9_TQ + px) * EST + 8 * p8) = o0;
-        *(h16x8*)(sE1 + (row * S9_TQ + px) * EST + 8 * p8) = o1;
-    }
-}
-// the dy tile of a tile: loads into registers / registers into LDS (the next tile's loads stay in flight in between)
-constexpr int S9_NDYE = (S9_TH + 8) * S9_DYW, S9_NDI = (S9_NDYE + 511) / 512;
-__device__ __forceinline__ void s9_fetch_dy(const Conv9SplitArgs& a, int b, int y0, int x0, int tid, float (&vdy)[S9_NDI]) {
-    const int rowf = (S9_TQ + 8) * a.Cout;
 #pragma unroll
-    for (int u = 0; u < S9_NDI; ++u) {
-        const int idx = tid + 512 * u;
-        const int f = idx % S9_DYW, ry = idx / S9_DYW;
-        const int gy = y0 - 4 + ry, gx = x0 - 4 + f / a.Cout, co = f % a.Cout;
-        const bool ok = idx < S9_NDYE && f < rowf && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
-        // (clamped address, unconditional load: a predicated prefetch would make hipcc drain vmcnt(0))
-        const size_t o = ok ? (((size_t)b * a.H + gy) * a.W + gx) * a.Cout + co : 0;
-        const float v = a.dy[o];
-        vdy[u] = ok ? v : 0.f;
+        for (int u = 0; u < 18; ++u) {
+            const int e = tid + 256 * (18 * h + u), ci = e & 31, n = (e >> 5) & 31, kh = e >> 10;
+            h16_t h0, h1;
+            s9_split(wq[u], sw, h0, h1);
+            const int o = (kh * 32 + n) * 32 + 8 * ((ci >> 3) ^ ((n >> 2) & 3)) + (ci & 7);
+            sW0[o] = h0;
+            sW1[o] = h1;
+        }
+    }
+    // staging: piece tid + 256 u = the eight channels 8 half .. 8 half + 7 of the chunk at pixel (row wv + 4 u, column pcol)
+    const int pcol = (tid >> 1) & 31, half = tid & 1;
+    const int frel = ((wv - 4) * a.W + (pcol - 4)) * 32 + 8 * half;           // floats from the tile's origin pixel (y0, x0), u = 0
+    const int fdst = (wv * S9G_TQ + pcol) * 16 + 8 * (half ^ ((pcol >> 3) & 1));
+    u32x4_t vin[8];
+    auto origin = [&](int tile, int& b, int& x0, int& y0) {
+        b = tile / (tiles_x * tiles_y);
+        const int tt = tile - b * (tiles_x * tiles_y);
+        x0 = (tt % tiles_x) * S9G_TWO;
+        y0 = (tt / tiles_x) * S9_TH;
+    };
+    auto fetch = [&](int tile, int c0) {
+        int b, x0, y0;
+        origin(tile, b, x0, y0);
+        const BufRsrc rx = dasr_make_rsrc(a.x + (size_t)b * a.H * a.W * 32, (size_t)a.H * a.W * 32 * sizeof(float));
+        // (masks, not selects on a condition: hipcc turns `column ok && row ok ? .. : DASR_OOB` into branches around the loads)
+        const unsigned cm = (unsigned)(x0 - 4 + pcol) < (unsigned)a.W ? 0u : ~0u;
+        const int base = (y0 * a.W + x0) * 32 + c0 + frel;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const unsigned m = cm | ((unsigned)(y0 - 4 + wv + 4 * u) < (unsigned)a.H ? 0u : ~0u);
+            const unsigned off = ((unsigned)((base + u * 4 * a.W * 32) * (int)sizeof(float)) & ~m) | (DASR_OOB & m);
+            vin[2 * u] = dasr_buffer_load16(rx, off);
+            vin[2 * u + 1] = dasr_buffer_load16(rx, off + 16);
+        }
+    };
+    // the shift-add: output tid + 256 u = (tile row orow, column ocol, channel co) - from sP float ospo + kw (PST + Cout) on,
+    // to float orel from the tile's origin pixel in y
+    int orow[S9G_NOUT], ocol[S9G_NOUT], ospo[S9G_NOUT], orel[S9G_NOUT];
+    float obias[S9G_NOUT];
+#pragma unroll
+    for (int u = 0; u < S9G_NOUT; ++u) {
+        const int idx = tid + 256 * u;
+        const bool in = idx < S9_TH * S9G_TWO * a.Cout;
+        const int co = idx % a.Cout, ox = (idx / a.Cout) % S9G_TWO, r = in ? idx / (a.Cout * S9G_TWO) : 0;
+        orow[u] = r;
+        ocol[u] = in ? ox : (1 << 28);                             // (past the tile's outputs: never inside the image)
+        ospo[u] = (r * S9G_TQ + ox) * S9G_PST + co;
+        orel[u] = (r * a.W + ox) * a.Cout + co;
+        obias[u] = a.bias ? a.bias[co] : 0.f;
+    }
+    const int pstep = S9G_PST + a.Cout;
+    const int asw = (li >> 3) & 1, bsw = (li >> 2) & 3;
+    const int ab = (2 * wv * S9G_TQ + li) * 16 + 8 * (lh ^ asw);   // this lane's piece of input row 2 wv; + 512 per row
+    const int wb = li * 32;                                        // ... of kernel row n = li, kh = 0; + 1024 per kh
+    // (tiles in linear order, tile = workgroup + 512 trips: the 8 x 8 tile blocks per XCD that correspond to the first form's
+    // order measured 5 % slower here - this form is bound by its own chain, not by where the halo is re-read from)
+    int tile = blockIdx.x;
+    if (tile < total) fetch(tile, 0);
+    for (; tile < total; tile += gridDim.x) {
+        const int ntile = tile + (int)gridDim.x < total ? tile + (int)gridDim.x : tile;      // (past the end: re-reads this tile)
+        int b, x0, y0;
+        origin(tile, b, x0, y0);
+        f32x16 acc[2];
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[m][r] = 0.f;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            DASR_LDS_BARRIER();                            // every wave is done with the previous chunk / tile (incl. its P image)
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                float f[8];
+                memcpy(f, &vin[2 * u], 16);
+                memcpy(f + 4, &vin[2 * u + 1], 16);
+                h16x8 p0, p1;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    h16_t h0, h1;
+                    s9_split(f[j], sx, h0, h1);
+                    p0[j] = h0; p1[j] = h1;
+                }
+                *(h16x8*)(sIn0 + fdst + u * 4 * S9G_TQ * 16) = p0;
+                *(h16x8*)(sIn1 + fdst + u * 4 * S9G_TQ * 16) = p1;
+            }
+            DASR_LDS_BARRIER();
+            fetch(c == 1 ? ntile : tile, c == 1 ? 0 : 16);     // the next chunk of this tile, or the first chunk of the next tile
+            {
+                // kh step: the operands of step kh + 1 are read while step kh multiplies
+                const int pw = 8 * ((2 * c + lh) ^ bsw);
+                h16x8 A0 = *(const h16x8*)(sIn0 + ab), A1 = *(const h16x8*)(sIn1 + ab);
+                h16x8 N0 = *(const h16x8*)(sIn0 + ab + 512), N1 = *(const h16x8*)(sIn1 + ab + 512);
+                h16x8 B0 = *(const h16x8*)(sW0 + wb + pw), B1 = *(const h16x8*)(sW1 + wb + pw);
+                DASR_SCHED_BARRIER();
+#pragma unroll
+                for (int kh = 0; kh < 9; ++kh) {
+                    const h16x8 a0 = A0, a1 = A1, n0 = N0, n1 = N1, b0 = B0, b1 = B1;
+                    A0 = n0; A1 = n1;
+                    if (kh + 1 < 9) {
+                        N0 = *(const h16x8*)(sIn0 + ab + (kh + 2) * 512); N1 = *(const h16x8*)(sIn1 + ab + (kh + 2) * 512);
+                        B0 = *(const h16x8*)(sW0 + wb + (kh + 1) * 1024 + pw); B1 = *(const h16x8*)(sW1 + wb + (kh + 1) * 1024 + pw);
+                    }
+                    acc[0] = s9_mma(a0, a1, b0, b1, acc[0]);
+                    acc[1] = s9_mma(n0, n1, b0, b1, acc[1]);
+                    if (kh + 1 < 9) DASR_SCHED_GROUP(0x100, 4);    // (hipcc otherwise sinks the reads to just before their use)
+                    DASR_SCHED_GROUP(0x8, 6);
+                }
+                DASR_SCHED_BARRIER();
+            }
+        }
+        DASR_LDS_BARRIER();
+        float* sP = (float*)smem;   // [8][32][PST]
+        if (li < S9G_PST) {
+#pragma unroll
+            for (int m = 0; m < 2; ++m)
+#pragma unroll
+                for (int g = 0; g < 16; ++g) {
+                    const int qx = (g & 3) + 8 * (g >> 2) + 4 * lh;
+                    sP[((2 * wv + m) * S9G_TQ + qx) * S9G_PST + li] = acc[m][g];
+                }
+        }
+        DASR_LDS_BARRIER();
+        const BufRsrc ry = dasr_make_rsrc((float*)a.out + (size_t)b * a.H * a.W * a.Cout, (size_t)a.H * a.W * a.Cout * sizeof(float));
+        const int obase = (y0 * a.W + x0) * a.Cout;
+#pragma unroll
+        for (int u = 0; u < S9G_NOUT; ++u) {
+            const bool ok = y0 + orow[u] < a.H && x0 + ocol[u] < a.W;
+            float v = 0.f;
+#pragma unroll
+            for (int kw = 0; kw < 9; ++kw) v += sP[ospo[u] + kw * pstep];
+            dasr_buffer_store4f(ry, ok ? (unsigned)((obase + orel[u]) * (int)sizeof(float)) : DASR_OOB, fmaf(v, inv, obias[u]));
+        }
     }
 }
+
+// ------------------------------------------------------------------------------------------ the E image (dgrad / wgrad)
+// E[row][px][k'] (two fp16 images) = sd * dy row image [Cout*px + k'], 0 for k' >= 9 Cout, the dy tile's rows y0-4 .. y0+11 with
+// Cout channels interleaved (zero outside the image).  Every dy value is scaled and split ONCE into two fp16 row images; a
+// 16-byte piece of E (row, px, 8 k') is eight consecutive fp16 of a row from any element offset: five aligned dwords and
+// v_alignbit_b32.  The wgrad's tile is 8 rows x 32 columns (below), the dgrad's 8 x 16.
+#define S9_TQ 32
+#define S9_DYW ((S9_TQ + 8) * 3 + 8)      // wgrad dy tile row stride: 40 px * 3 ch + pad = 128
+constexpr int S9_NDYE = (S9_TH + 8) * S9_DYW, S9_NDI = S9_NDYE / 512;
+static_assert(S9_NDI * 512 == S9_NDYE && S9_DYW == 128, "dy tile: whole trips of 512 threads, four threads' elements one column");
 
 // ------------------------------------------------------------------------------------------ dgrad
 // 256 threads, TWO workgroups per CU (74.9 KB of LDS each) whose phases overlap: while one stages dy / builds its E image /
@@ -523,7 +678,10 @@ __global__ void __launch_bounds__(256, 2) k_conv9_dgrad_split(Conv9SplitArgs a) 
 // tile row w, all nine kh (9 accumulators = dW[kh] as a 32 ci x 32 k' tile).  K = pixels, so both operands are read
 // TRANSPOSED from pixel-major LDS tiles with ds_read_b64_tr_b16 (on 16-bit fp16 elements): A = x^T ([ci][pixel]),
 // B = E^T.  Each wave writes its own slab [9][32][32] (times the inverse of the two scales); k_conv9_wgrad_reduce_split
-// sums the slabs and un-folds k'.
+// sums the slabs and un-folds k'.  The dy tile is split once into two fp16 row images and E built from them (see above: the
+// piece (px, 8 k') of rows r0, r0 + 4, .. per thread); the loads go through range-checked descriptors with what does not
+// depend on the tile worked out once, and the barriers are LDS-only: the next tile's loads stay in flight across the E
+// build AND the MFMA phase.
 __device__ __forceinline__ h16x4 s9_read_tr16(const h16_t* p) {
     const bf16x4 r = lds_read_tr16((const bf16_t*)p);
     h16x4 v;
@@ -538,8 +696,9 @@ __global__ void __launch_bounds__(512) k_conv9_wgrad_split(Conv9SplitArgs a) {
     h16_t* sX1 = sX0 + NX;
     h16_t* sE0 = sX1 + NX;                                         // [16][32][EST]
     h16_t* sE1 = sE0 + NE;
-    float* sDy = (float*)(sE1 + NE);                               // [16][DYW]
-    float* s_red = sDy + S9_NDYE;                                  // [32]
+    h16_t* sH0 = sE1 + NE;                                         // [16][DYW]: the dy tile, split ONCE per value
+    h16_t* sH1 = sH0 + S9_NDYE;
+    float* s_red = (float*)(sH1 + S9_NDYE);                        // [32]
     const int tid = threadIdx.x, lane = tid & 63, wv = DASR_UNIFORM((int)(tid >> 6)), li = lane & 31, lh = lane >> 5;
     const int tiles_x = (a.W + S9_TQ - 1) / S9_TQ, tiles_y = (a.H + S9_TH - 1) / S9_TH;
     const int ci0 = blockIdx.x * 32;
@@ -555,6 +714,20 @@ __global__ void __launch_bounds__(512) k_conv9_wgrad_split(Conv9SplitArgs a) {
     constexpr int NXP = S9_TH * S9_TQ * 8 / 512;                   // 4 pieces of 16 bytes (4 channels) per thread
     u32x4_t vx[NXP];
     float vdy[S9_NDI];
+    // dy tile, rows y0-4 .. y0+11, columns x0-4 .. x0+35, Cout channels interleaved: element tid + 512 u is float f = tid & 127
+    // of tile row r0 + 4 u - the column and the division by Cout are the same for every u and every tile
+    const int KK = 9 * a.Cout;
+    const int r0 = DASR_UNIFORM((int)(tid >> 7)), dyf = tid & (S9_DYW - 1);
+    const int dyx = dyf < (S9_TQ + 8) * a.Cout ? dyf / a.Cout - 4 : (1 << 28);       // (the row's padding: never inside the image)
+    const int dyo = ((r0 - 4) * a.W - 4) * a.Cout + dyf;                             // floats from the tile's origin pixel (y0, x0), u = 0
+    // E: this thread builds the piece (px, p8) of rows r0, r0 + 4, .. - eight fp16 from element es of the row, any parity
+    const int p8 = tid & 3, epx = (tid >> 2) & 31;
+    const int es = a.Cout * epx + 8 * p8;
+    const unsigned ebits = (es & 1) * 16;
+    const int esrc = r0 * S9_DYW + (es & ~1), edst = (r0 * S9_TQ + epx) * EST + 8 * p8;
+    unsigned em[4];
+#pragma unroll
+    for (int d = 0; d < 4; ++d) em[d] = (8 * p8 + 2 * d < KK ? 0xffffu : 0u) | (8 * p8 + 2 * d + 1 < KK ? 0xffff0000u : 0u);
     auto origin = [&](int tile, int& b, int& x0, int& y0) {
         const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y;
         b = tile / (tiles_x * tiles_y);
@@ -573,16 +746,26 @@ __global__ void __launch_bounds__(512) k_conv9_wgrad_split(Conv9SplitArgs a) {
                                                ? (unsigned)(((gy * a.W + gx) * a.Cin + ci0 + 4 * q8) * (int)sizeof(float))
                                                : DASR_OOB);
         }
-        s9_fetch_dy(a, b, y0, x0, tid, vdy);
+        // (zero outside the image: the descriptor's range check; masks, not selects, so that hipcc does not branch around loads)
+        const BufRsrc rd = dasr_make_rsrc(a.dy + (size_t)b * a.H * a.W * a.Cout, (size_t)a.H * a.W * a.Cout * sizeof(float));
+        const unsigned cm = (unsigned)(x0 + dyx) < (unsigned)a.W ? 0u : ~0u;
+        const int base = (y0 * a.W + x0) * a.Cout + dyo;
+#pragma unroll
+        for (int u = 0; u < S9_NDI; ++u) {
+            const unsigned m = cm | ((unsigned)(y0 + r0 - 4 + 4 * u) < (unsigned)a.H ? 0u : ~0u);
+            vdy[u] = dasr_buffer_load4f(rd, ((unsigned)((base + 4 * u * a.W * a.Cout) * (int)sizeof(float)) & ~m) | (DASR_OOB & m));
+        }
     };
     int tile = blockIdx.y;
     if (tile < a.ntiles) fetch(tile);
     for (; tile < a.ntiles; tile += a.P) {
-        __syncthreads();                         // every wave is done with the previous tile
+        DASR_LDS_BARRIER();                      // every wave is done with the previous tile
 #pragma unroll
         for (int u = 0; u < S9_NDI; ++u) {
-            const int idx = tid + 512 * u;
-            if (idx < S9_NDYE) sDy[idx] = vdy[u];
+            h16_t h0, h1;
+            s9_split(vdy[u], sd, h0, h1);
+            sH0[tid + 512 * u] = h0;
+            sH1[tid + 512 * u] = h1;
         }
 #pragma unroll
         for (int u = 0; u < NXP; ++u) {
@@ -599,10 +782,22 @@ __global__ void __launch_bounds__(512) k_conv9_wgrad_split(Conv9SplitArgs a) {
             *(h16x4*)(sX0 + (idx >> 3) * 32 + 4 * (idx & 7)) = p0;
             *(h16x4*)(sX1 + (idx >> 3) * 32 + 4 * (idx & 7)) = p1;
         }
-        __syncthreads();
+        DASR_LDS_BARRIER();
         fetch(tile + a.P < a.ntiles ? tile + a.P : tile);
-        s9_build_E<EST>(a, sDy, sE0, sE1, sd, tid);
-        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < (S9_TH + 8) / 4; ++i) {
+            const u32a_t* s0 = (const u32a_t*)(sH0 + esrc + i * 4 * S9_DYW);
+            const u32a_t* s1 = (const u32a_t*)(sH1 + esrc + i * 4 * S9_DYW);
+            u32x4_t o0, o1;
+#pragma unroll
+            for (int d = 0; d < 4; ++d) {
+                o0[d] = s9d_fsh(s0[d], s0[d + 1], ebits) & em[d];
+                o1[d] = s9d_fsh(s1[d], s1[d + 1], ebits) & em[d];
+            }
+            *(u32x4a_t*)(sE0 + edst + i * 4 * S9_TQ * EST) = o0;
+            *(u32x4a_t*)(sE1 + edst + i * 4 * S9_TQ * EST) = o1;
+        }
+        DASR_LDS_BARRIER();
         // K-step = 16 consecutive pixels of this wave's row
 #pragma unroll
         for (int s = 0; s < S9_TQ / 16; ++s) {
@@ -637,21 +832,37 @@ __global__ void __launch_bounds__(512) k_conv9_wgrad_split(Conv9SplitArgs a) {
         }
 }
 
-// dw[kh][kw][ci][co] = sum over slabs of slab[cig][kh][ci%32][(8-kw)*Cout+co]; the slab range is split over
-// blockIdx.y (partial sums meet in the zeroed dw through float atomics)
-__global__ void __launch_bounds__(256) k_conv9_wgrad_reduce_split(const float* __restrict__ slabs, float* __restrict__ dw,
-                                                                  int Cin, int Cout, int nslabs, int cgroups, int per_y) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int n = 81 * Cin * Cout;
-    if (i >= n) return;
-    const int co = i % Cout, ci = (i / Cout) % Cin, kw = (i / (Cout * Cin)) % 9, kh = i / (Cout * Cin * 9);
-    const int np = (8 - kw) * Cout + co;
-    const float* p = slabs + (size_t)(ci / 32) * (9 * 32 * 32) + (kh * 32 + (ci & 31)) * 32 + np;
-    const int s0 = blockIdx.y * per_y;
-    const int s1 = s0 + per_y < nslabs ? s0 + per_y : nslabs;
+// dw[kh][kw][ci][co] = sum over slabs of slab[cig][kh][ci%32][(8-kw)*Cout+co], every element's slabs in a fixed order (bitwise
+// repeatable from launch to launch, no atomics, nothing to clear beforehand).  A workgroup owns one slab row (cig, kh, ci % 32:
+// 32 k', 128 contiguous bytes); its 16 thread groups sum the slabs q, q + 16, ... with eight loads in flight per thread (the
+// slabs were just written: the latency chain, not the bytes, is what the launch waits for) and meet in LDS.
+__global__ void __launch_bounds__(512) k_conv9_wgrad_reduce_split(const float* __restrict__ slabs, float* __restrict__ dw,
+                                                                  int Cin, int Cout, int nslabs, int cgroups) {
+    __shared__ float part[16][32];
+    const int np = threadIdx.x & 31, q = threadIdx.x >> 5;
+    const int row = blockIdx.x, cl = row & 31, kh = (row >> 5) % 9, cig = row / (9 * 32);
+    const bool in = np < 9 * Cout;
     float acc = 0.f;
-    for (int s = s0; s < s1; ++s) acc += p[(size_t)s * cgroups * (9 * 32 * 32)];
-    atomicAdd(&dw[i], acc);
+    if (in) {
+        const float* p = slabs + (size_t)cig * (9 * 32 * 32) + (kh * 32 + cl) * 32 + np;
+        const size_t st = (size_t)cgroups * (9 * 32 * 32);
+        for (int s0 = q; s0 < nslabs; s0 += 8 * 16) {
+            float v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = s0 + 16 * u < nslabs ? p[(size_t)(s0 + 16 * u) * st] : 0.f;
+#pragma unroll
+            for (int u = 0; u < 8; ++u) acc += v[u];
+        }
+    }
+    part[q][np] = acc;
+    __syncthreads();
+    if (q == 0 && in) {
+        float r = part[0][np];
+#pragma unroll
+        for (int t = 1; t < 16; ++t) r += part[t][np];
+        const int kw = 8 - np / Cout, co = np % Cout;
+        dw[(((size_t)kh * 9 + kw) * Cin + cig * 32 + cl) * Cout + co] = r;
+    }
 }
 
 // ------------------------------------------------------------------------------------------ host side
@@ -662,12 +873,18 @@ bool conv9_split_supported(const ConvGeom& g) {
 int conv9_split_fwd(const ConvGeom& g, const float* x, const float* xmax, const float* w, const float* wmax, const float* bias,
                     float* y, void* stream) {
     Conv9SplitArgs a{x, w, bias, nullptr, y, xmax, nullptr, wmax, g.B, g.H, g.W, g.Cin, g.Cout, 0, 0, 0};
+    if (g.Cin == 32 && (dasr_get_conv_bf16_impl() & 8192) == 0) {      // (+ 8192: the first form, A/B and tests)
+        const int tiles = ((g.W + S9G_TWO - 1) / S9G_TWO) * ((g.H + S9_TH - 1) / S9_TH) * g.B;
+        const int cap = (dasr_get_conv_bf16_impl() & 3) == 2 ? 3 : 512;    // (impl 2, tests: long per-workgroup tile lists)
+        DASR_LAUNCH(k_conv9_fwd_split, dim3(tiles < cap ? tiles : cap), dim3(256), S9G_LDS, stream, a);     // two persistent workgroups per CU
+        DASR_RETURN_LAUNCH_STATUS();
+    }
     const int TWO = S9F_TQ - 8;
     const int tiles = ((g.W + TWO - 1) / TWO) * ((g.H + S9_TH - 1) / S9_TH) * g.B;
     const size_t lds = sizeof(h16_t) * (size_t)(2 * (S9_TH + 8) * S9F_TQ * S9F_ST + 2 * (g.Cin / 16) * 9 * 32 * S9F_ST) + 128;
     const int cap = (dasr_get_conv_bf16_impl() & 3) == 2 ? 3 : 256;    // (impl 2, tests: long per-workgroup tile lists)
     a.P = (tiles >= 256 && cap == 256 && (dasr_get_conv_bf16_impl() & 4096) == 0) ? 1 : 0;      // XCD-blocked tile order (+ 4096: linear, A/B)
-    DASR_LAUNCH(k_conv9_fwd_split, dim3(tiles < cap ? tiles : cap), dim3(512), lds, stream, a);     // one persistent workgroup per CU
+    DASR_LAUNCH(k_conv9_fwd_split_1wg, dim3(tiles < cap ? tiles : cap), dim3(512), lds, stream, a);     // one persistent workgroup per CU
     DASR_RETURN_LAUNCH_STATUS();
 }
 static int conv9_split_dgrad_launch(const ConvGeom& g, Conv9SplitArgs& a, bool fuse, void* stream) {
@@ -713,12 +930,8 @@ int conv9_split_wgrad(const ConvGeom& g, const float* x, const float* xmax, cons
     const size_t lds = sizeof(h16_t) * (size_t)(2 * S9_TH * S9_TQ * 32 + 2 * (S9_TH + 8) * S9_TQ * 32) +
                        sizeof(float) * (size_t)(S9_NDYE + 32);
     DASR_LAUNCH(k_conv9_wgrad_split, dim3(g.Cin / 32, P), dim3(512), lds, stream, a);
-    const int n = 81 * g.Cin * g.Cout;
-    hipError_t e = hipMemsetAsync(dw, 0, sizeof(float) * n, (hipStream_t)stream);
-    if (e != hipSuccess) return (int)e;
-    const int nslabs = P * 8, ysplit = nslabs >= 64 ? 32 : 1;
-    DASR_LAUNCH(k_conv9_wgrad_reduce_split, dim3(dasr_cdiv(n, 256), ysplit), dim3(256), 0, stream, (const float*)workspace, dw,
-                g.Cin, g.Cout, nslabs, g.Cin / 32, (nslabs + ysplit - 1) / ysplit);
+    DASR_LAUNCH(k_conv9_wgrad_reduce_split, dim3((g.Cin / 32) * 9 * 32), dim3(512), 0, stream, (const float*)workspace, dw, g.Cin,
+                g.Cout, P * 8, g.Cin / 32);
     DASR_RETURN_LAUNCH_STATUS();
 }
 

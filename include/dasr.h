@@ -403,7 +403,9 @@ int dasr_conv2d_epilogue_bwd_bf16(const unsigned short* dy, const unsigned short
  * + 512 = ... at 64 produced channels with all nine kernel slices of a chunk per barrier; + 1024 = swap its two eight-wave
  * forms (128 produced channels: kernel-row K-steps instead of channel halves x kernel columns; 64: the reverse);
  * + 2048 = the bf16 dynamic-conv forward (dasr_sean_fwd_bf16) with 4 instead of 8 channels per lane;
- * + 4096 = the 9x9 split forward with the linear instead of the XCD-blocked tile order.
+ * + 4096 = the first form of the 9x9 split forward (+ 8192) with the linear instead of the XCD-blocked tile order;
+ * + 8192 = the 9x9 split forward in its first form (one 512-thread workgroup per CU on 8 x 56 tiles; default at Cin = 32: two
+ * 256-thread workgroups per CU on 8 x 24 tiles in linear order, the same bits).
  * For A/B measurements and tests; process-wide, not thread-safe against concurrent launches.
  * dasr_conv_bf16_v2_launches(): how many times the persistent kernel has been launched by this process. */
 int dasr_set_conv_bf16_impl(int impl);
