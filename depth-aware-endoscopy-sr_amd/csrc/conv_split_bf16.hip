@@ -71,6 +71,9 @@ struct ConvSplitArgs {
     const float* xmax;       // NP = 2: max |x| and max |w| in device memory (dasr_absmax); NP = 3: unused
     const float* wmax;
     float* ymax;             // (may be null) raised to max |y| of what the epilogue stores
+    // the fused dgrad (dasr_conv3x3_dgrad_act_split2, FUSE epilogue only; the other kernels never read these)
+    const float* xact;       // [B,H,W,Cout] the producer's saved output behind its activation (/ PixelShuffle(2))
+    int fact, fps;           // its activation; 1: y is [B,H,W,Cout], 2: y is the producer's conv output [B,H/2,W/2,4 Cout]
 };
 
 template <int N>
@@ -314,6 +317,132 @@ __device__ __forceinline__ void sp_epilogue(f32x16 (&acc)[RW][NT], const ConvSpl
                 }
             }
             DASR_WAVE_SYNC();
+        }
+    }
+}
+
+// ---- epilogue of the fused dgrad (dasr_conv3x3_dgrad_act_split2; one 32-channel tile, two tile rows per wave): the sums of
+// the plain epilogue (x inv, + the old dprev when accumulating) times the derivative of the PRODUCER's activation, read from
+// its saved output x_act at the address the sum belongs to - one more read of the tensor instead of the read-read-write
+// pass of k_conv_epilogue_bwd_*.  The x_act loads are issued before the scratch round trip and land under it.
+//   fps = 1: the lane map of the plain epilogue (8 channels of one pixel per lane and trip).
+//   fps = 2: y is the producer's conv output [B,H/2,W/2,4 Cout], y[.., y >> 1, x >> 1, 4c + 2(y & 1) + (x & 1)].  A wave owns tile
+//     rows 2w, 2w + 1 and y0, x0 are even: the 2 x 2 block of a channel lies in one wave.  A lane takes 4 channels of a pixel
+//     PAIR from the scratch row of each of its two tile rows (one after the other, through the same one-row scratch: the
+//     first row's 8 values wait in registers) and stores the 16 consecutive channels 4c .. 4c + 15 of the conv pixel: 64 bytes.
+// Same single multiply per element as the standalone pass: the result is bit-equal to it.
+template <int NP>
+__device__ __forceinline__ void sp_epilogue_act(f32x16 (&acc)[2][1], const ConvSplitArgs& a, char* const scr, const float* sBias,
+                                                const float inv, const int x0, const int y0, const int n0, const int bb,
+                                                const int rbase, const int lane, const int li, const int lh, float& om) {
+    const int wvalid = a.W - x0;
+    const float dneg = a.fact == DASR_ACT_RELU ? 0.f : (a.fact == DASR_ACT_LRELU02 ? 0.2f : 1.f);
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (a.fps == 1) {
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+            const int gy = y0 + rbase + m;
+            float4 xa[2][2];
+            size_t idx[2];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int v = lane + 64 * u, pix = v >> 2, cg = v & 3;
+                const bool ok = gy < a.H && pix < wvalid;
+                idx[u] = (((size_t)bb * a.H + gy) * a.W + x0 + pix) * a.Cout + n0 + 8 * cg;
+                xa[u][0] = z4; xa[u][1] = z4;
+                if (ok) { xa[u][0] = *(const float4*)(a.xact + idx[u]); xa[u][1] = *(const float4*)(a.xact + idx[u] + 4); }
+            }
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                f32x4 pk = {acc[m][0][4 * g], acc[m][0][4 * g + 1], acc[m][0][4 * g + 2], acc[m][0][4 * g + 3]};
+                *(f32x4*)(scr + li * SP_EPITCH + (8 * g + 4 * lh) * 4) = pk;
+            }
+            DASR_WAVE_SYNC();
+            if (gy < a.H) {
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const int v = lane + 64 * u, pix = v >> 2, cg = v & 3;
+                    if (pix >= wvalid) continue;
+                    const float4 lo = *(const float4*)(scr + pix * SP_EPITCH + 32 * cg);
+                    const float4 hi = *(const float4*)(scr + pix * SP_EPITCH + 32 * cg + 16);
+                    float o[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+                    if (NP == 2) {
+                        const float* bp = sBias + n0 + 8 * cg;
+#pragma unroll
+                        for (int t = 0; t < 8; ++t) o[t] = fmaf(o[t], inv, bp[t]);
+                    }
+                    float* yp = a.y + idx[u];
+                    if (a.accumulate) {
+                        const float4 o0 = *(const float4*)yp, o1 = *(const float4*)(yp + 4);
+                        o[0] += o0.x; o[1] += o0.y; o[2] += o0.z; o[3] += o0.w;
+                        o[4] += o1.x; o[5] += o1.y; o[6] += o1.z; o[7] += o1.w;
+                    }
+                    const float xv[8] = {xa[u][0].x, xa[u][0].y, xa[u][0].z, xa[u][0].w, xa[u][1].x, xa[u][1].y, xa[u][1].z, xa[u][1].w};
+#pragma unroll
+                    for (int t = 0; t < 8; ++t) o[t] *= xv[t] > 0.f ? 1.f : dneg;
+                    *(float4*)yp = make_float4(o[0], o[1], o[2], o[3]);
+                    *(float4*)(yp + 4) = make_float4(o[4], o[5], o[6], o[7]);
+                    om = dasr_amax4(dasr_amax4(om, make_float4(o[0], o[1], o[2], o[3])), make_float4(o[4], o[5], o[6], o[7]));
+                }
+            }
+            DASR_WAVE_SYNC();
+        }
+    } else {
+        const int gy0 = y0 + rbase;                     // even, H even: the wave's two rows are inside or outside together
+        const bool rowok = gy0 < a.H;
+        float4 xa[2][2][2];                             // [tile row][trip][pixel of the pair]
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const int v = lane + 64 * u, cq = v & 7, px = 2 * (v >> 3) + j;
+                    const bool ok = rowok && px < wvalid;
+                    xa[m][u][j] = z4;
+                    if (ok) xa[m][u][j] = *(const float4*)(a.xact + (((size_t)bb * a.H + gy0 + m) * a.W + x0 + px) * a.Cout + n0 + 4 * cq);
+                }
+        float r[2][2][2][4];
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                f32x4 pk = {acc[m][0][4 * g], acc[m][0][4 * g + 1], acc[m][0][4 * g + 2], acc[m][0][4 * g + 3]};
+                *(f32x4*)(scr + li * SP_EPITCH + (8 * g + 4 * lh) * 4) = pk;
+            }
+            DASR_WAVE_SYNC();
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const int v = lane + 64 * u, cq = v & 7, px = 2 * (v >> 3) + j;
+                    const float4 s = *(const float4*)(scr + px * SP_EPITCH + 16 * cq);
+                    float o[4] = {s.x, s.y, s.z, s.w};
+                    if (NP == 2) {
+                        const float* bp = sBias + n0 + 4 * cq;
+#pragma unroll
+                        for (int t = 0; t < 4; ++t) o[t] = fmaf(o[t], inv, bp[t]);
+                    }
+                    const float xv[4] = {xa[m][u][j].x, xa[m][u][j].y, xa[m][u][j].z, xa[m][u][j].w};
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) r[m][u][j][t] = o[t] * (xv[t] > 0.f ? 1.f : dneg);
+                }
+            DASR_WAVE_SYNC();
+        }
+        if (rowok) {
+            const size_t Cq = (size_t)4 * a.Cout;
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int v = lane + 64 * u, cq = v & 7, P = v >> 3;
+                if (2 * P >= wvalid) continue;          // (W even, x0 even: the pair is inside or outside together)
+                float* yp = a.y + (((size_t)bb * (a.H >> 1) + (gy0 >> 1)) * (a.W >> 1) + (x0 >> 1) + P) * Cq + 4 * (n0 + 4 * cq);
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const float4 q = make_float4(r[0][u][0][t], r[0][u][1][t], r[1][u][0][t], r[1][u][1][t]);
+                    *(float4*)(yp + 4 * t) = q;
+                    om = dasr_amax4(om, q);
+                }
+            }
         }
     }
 }
@@ -569,7 +698,9 @@ __global__ void __launch_bounds__(64 * (SP_TH / RW), RW == 4 ? 1 : 2) k_conv3x3_
 // 3 KB), so ALL NINE are fetched with the halo chunk, double-buffered by chunk: one wait + barrier per CHUNK (108 MFMAs per
 // wave), the nine taps run free of synchronisation and the compiler pipelines reads, splits and MFMAs across them.
 // (NT = 2, fp16 x 2 only, A/B behind impl + 512: the same one-barrier-per-chunk form for 64 produced channels - nine 4 KB slices.)
-template <int NP, int NT = 1>
+// (FUSE, fp16 x 2 / NT = 1: the dgrad with the producer's activation / PixelShuffle(2) backward in its epilogue - the same item
+// loop, sp_epilogue_act in place of sp_epilogue.)
+template <int NP, int NT = 1, bool FUSE = false>
 __global__ void __launch_bounds__(SP_NTHR, 2) k_conv3x3_split_n32(ConvSplitArgs a) {
     DASR_DYN_SMEM(smem);
     typedef SpFrag<NP> F;
@@ -734,7 +865,8 @@ __global__ void __launch_bounds__(SP_NTHR, 2) k_conv3x3_split_n32(ConvSplitArgs 
         // accumulate and the PixelShuffle(2) store as in conv_mfma.hip's epilogue
         DASR_RAW_BARRIER();
         char* const scr = sH + (par ^ 1) * SP_HBYTES + wv * (32 * SP_EPITCH);
-        sp_epilogue<NT, NP>(acc, a, scr, sBias, sc.inv, x0, y0, n0, bb, 2 * wv, lane, li, lh, om);
+        if constexpr (FUSE) sp_epilogue_act<NP>(acc, a, scr, sBias, sc.inv, x0, y0, n0, bb, 2 * wv, lane, li, lh, om);
+        else                sp_epilogue<NT, NP>(acc, a, scr, sBias, sc.inv, x0, y0, n0, bb, 2 * wv, lane, li, lh, om);
         if (!has_next) break;
         item = nitem; x0 = nx0; y0 = ny0; n0 = nn0; bb = nb;
     }
@@ -952,7 +1084,11 @@ static int sp_launch(ConvSplitArgs& a, void* stream) {
     if (lds > 160 * 1024) return DASR_E_UNSUPPORTED;
     const dim3 grid(8 * a.G8);
     // (impl + 256, A/B: the four-wave form - four tile rows per wave - of the fp16 x 2 kernel at 128 produced channels)
-    if (NT == 4 && NP == 2 && (dasr_get_conv_bf16_impl() & 256) != 0)
+    if (a.xact) {                                              // the fused dgrad: 32 produced channels, fp16 x 2 only
+        if (NT != 1 || NP != 2) return DASR_E_UNSUPPORTED;
+        DASR_LAUNCH((k_conv3x3_split_n32<2, 1, true>), grid, dim3(SP_NTHR), lds, stream, a);
+    }
+    else if (NT == 4 && NP == 2 && (dasr_get_conv_bf16_impl() & 256) != 0)
         DASR_LAUNCH((k_conv3x3_split<4, 2, 4>), grid, dim3(256), lds, stream, a);
     // fp16 x 2, 128 produced channels: the channel-halves / kernel-column form (128 -> 128 forward 284 -> 279 us, 64 -> 256 286 ->
     // 278, 32 -> 128 at 512 x 640 1342 -> 1295; dgrads unchanged); at 64 produced channels it is no faster (64 -> 32 at 256 x 320:
@@ -1009,6 +1145,27 @@ extern "C" int dasr_conv3x3_dgrad_split2(const float* dconv, const float* dmax, 
                                          float* dx, int accumulate, int B, int H, int W, int Cin, int Cout, void* stream) {
     DASR_CHECK_PTR(dmax); DASR_CHECK_PTR(wmax);
     return sp_dgrad(dconv, dmax, w_split, wmax, dx, accumulate, B, H, W, Cin, Cout, stream);
+}
+// ... with the producer's activation (/ PixelShuffle(2)) backward in the epilogue: the 32-produced-channel kernel only (the HR
+// tail: HBM-bound, so the trade is one read of x_act for the read-read-write pass; the 128-channel kernels sit at the power
+// limit and lost with the same epilogue, graph.FUSE_DGRAD_ACT)
+extern "C" int dasr_conv3x3_dgrad_act_supported(int H, int W, int Cin, int Cout, int act, int ps_r, int accumulate) {
+    if (Cin != 32 || !dasr_conv3x3_split_supported(H, W, Cin, Cout)) return 0;
+    if (act != DASR_ACT_NONE && act != DASR_ACT_RELU && act != DASR_ACT_LRELU02) return 0;
+    if (ps_r == 1) return 1;
+    return (ps_r == 2 && (H % 2) == 0 && (W % 2) == 0 && !accumulate) ? 1 : 0;
+}
+extern "C" int dasr_conv3x3_dgrad_act_split2(const float* dconv, const float* dmax, const unsigned short* w_split, const float* wmax,
+                                             const float* x_act, float* dprev, float* dprev_amax, int accumulate, int B, int H,
+                                             int W, int Cin, int Cout, int act, int ps_r, void* stream) {
+    DASR_CHECK_PTR(dconv); DASR_CHECK_PTR(dmax); DASR_CHECK_PTR(w_split); DASR_CHECK_PTR(wmax); DASR_CHECK_PTR(x_act);
+    DASR_CHECK_PTR(dprev);
+    DASR_CHECK_SHAPE(B > 0);
+    if (!dasr_conv3x3_dgrad_act_supported(H, W, Cin, Cout, act, ps_r, accumulate)) return DASR_E_UNSUPPORTED;
+    const size_t mode1 = (size_t)9 * 2 * Cin * Cout;
+    ConvSplitArgs a{dconv, (const bf16_t*)w_split + mode1, nullptr, nullptr, dprev, B, H, W, Cout, Cin,
+                    accumulate ? 1 : 0, DASR_ACT_NONE, 1, 0, 0, 0, 0, 0, 0, dmax, wmax, dprev_amax, x_act, act, ps_r};
+    return sp_launch<2>(a, stream);
 }
 
 // ------------------------------------------------------------------------------------------ weight gradient

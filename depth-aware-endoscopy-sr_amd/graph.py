@@ -21,13 +21,21 @@ from .tape import Tape, Var, accum
 # before the split kernels existed, it removed the epilogue-backward passes (26 -> 6 ms per 4 steps) but the masked
 # epilogue's extra 4-byte loads and the scattered un-shuffle stores were not hidden under matrix work: the 9x9 dgrad went
 # 3.6 -> 6.2 ms and the 128->128 dgrad 0.82 -> 1.14 ms, a net loss of 4-10 % of the step.  Kept as a tested entry point for
-# shapes where the producer tensor is small.
+# shapes where the producer tensor is small.  (On the split path the same fusion runs where it trades bytes for bytes, in the
+# HBM-bound 32-channel dgrads: FUSE_SPLIT_DGRAD_ACT below.)
 FUSE_DGRAD_ACT = False
 # dasr_conv9_dgrad_act_split2 (csrc/conv9_split.hip) is what runs for the last upscale layer -> 9x9 output convolution pair
 # of the fp32 path: the fp16 x 2 split dgrad holds the whole 2 x 2 block of a channel in one lane, reads the saved activation
 # while it multiplies and stores dprev as 512-byte runs, so d(act) - the largest tensor of the step - is never written or
 # re-read and the k_conv_epilogue_bwd_ps<2> pass of that layer is gone (profiles/c9_dgrad_act_*).
 FUSE_C9_DGRAD_ACT = True
+# dasr_conv3x3_dgrad_act_split2 (csrc/conv_split_bf16.hip): the fp16 x 2 split dgrads that PRODUCE 32 channels - the HR tail
+# behind upscale1: 32 -> 32 and 32 -> 128 layers - apply the producer's activation (/ PixelShuffle(2)) backward in their
+# epilogue when they are the last gradient contribution to their input (residual layers: the accumulating dgrad; the
+# derivative multiplies the sum).  That kernel is HBM-bound, not power-limited like the 128-channel ones FUSE_DGRAD_ACT lost
+# on: one more read of the tensor replaces the read-read-write pass of k_conv_epilogue_bwd_* (DESIGN.md 4.11, 8;
+# profiles/tail_dgrad_act_*).  Dgrads that produce 64 channels (upscale1.3, head.2) stay on the standalone pass.
+FUSE_SPLIT_DGRAD_ACT = True
 
 # Run the depth-map branch of the SEANs on a side HIP stream (forward and backward).
 SIDE_STREAM = True
@@ -377,6 +385,9 @@ def conv(tape, x, w, bias=None, *, stride=1, pad=1, transposed=False, act=ops.AC
     if (act != ops.ACT_NONE or ps_r > 1) and residual is None:
         out.epilogue = (act, ps_r)
         out.epilogue_split = isinstance(w.split, tuple)
+    if act != ops.ACT_NONE or ps_r > 1:              # ... and for act(conv + residual) layers too (FUSE_SPLIT_DGRAD_ACT)
+        out.act_rec = (act, ps_r)
+        out.epilogue_split = isinstance(w.split, tuple)
     KH, KW, Cin, Cout = w.data.shape[1:]
     wshape = (KH, KW, Cin, Cout)
     B, H, W_, _ = x.data.shape
@@ -455,6 +466,18 @@ def conv(tape, x, w, bias=None, *, stride=1, pad=1, transposed=False, act=ops.AC
                                                     amax=want_amax(tape, dconv, (B, H // 2, W_ // 2, 4 * Cin))
                                                     if x.epilogue_split else None)
                 x.grad_is_preact = True
+            elif (FUSE_SPLIT_DGRAD_ACT and isinstance(w.split, tuple) and not _is_c9(w) and Cin == 32 and f32
+                  and x.act_rec is not None and x.grads_in + 1 == x.uses
+                  and ops.conv3x3_dgrad_act_supported(x.data.shape, Cout, x.act_rec[0], x.act_rec[1], x.grad is not None)):
+                # the last contribution to x = [PixelShuffle(2)] act(prev conv [+ residual]): write d(prev conv output);
+                # an earlier contribution (x as a block's residual) is summed in before the derivative applies
+                if dmax is None:
+                    dmax = _amax_t(dconv)
+                r = x.act_rec[1]
+                x.grad = ops.conv3x3_dgrad_act_split2(dconv, dmax, w.split, x.data, x.act_rec[0], r, out=x.grad,
+                                                      amax=want_amax(tape, dconv, (B, H // r, W_ // r, r * r * Cin))
+                                                      if x.epilogue_split else None)
+                x.grad_is_preact = True
             elif _is_c9(w):
                 if dmax is None:
                     dmax = _amax_t(dconv)
@@ -472,6 +495,7 @@ def conv(tape, x, w, bias=None, *, stride=1, pad=1, transposed=False, act=ops.AC
                 x.grad = ops.conv2d_dgrad(dconv, w.data, x.data.shape, stride, pad, transposed, out_dtype=x.data.dtype)
             else:
                 ops.conv2d_dgrad(dconv, w.data, x.data.shape, stride, pad, transposed, out=x.grad)
+            x.grads_in += 1
         if residual is not None:
             accum(residual, dconv)
 

@@ -586,6 +586,26 @@ def conv3x3_dgrad_split2(dconv, dmax, ws, x_shape, out=None):
     return out
 
 
+def conv3x3_dgrad_act_supported(x_shape, Cout, act, ps_r, accumulate=False):
+    B, H, W, Cin = x_shape
+    return bool(_lib.get().dasr_conv3x3_dgrad_act_supported(H, W, Cin, Cout, act, ps_r, 1 if accumulate else 0))
+
+
+def conv3x3_dgrad_act_split2(dconv, dmax, ws, x_act, act, ps_r, out=None, amax=None):
+    """conv3x3_dgrad_split2 with the producer's activation / PixelShuffle(2) backward in its epilogue (32 produced channels):
+    x_act [B,H,W,Cin] is the convolution's saved input.  ps_r = 1: returns dprev [B,H,W,Cin], into ``out`` =
+    (dgrad + out) * act'(x_act) when given; ps_r = 2: dprev [B,H/2,W/2,4 Cin].  max |dprev| is left in ``amax`` when given."""
+    B, H, W, Cin = x_act.shape
+    Cout = dconv.shape[3]
+    acc = out is not None
+    if out is None:
+        out = empty((B, H // 2, W // 2, 4 * Cin) if ps_r == 2 else (B, H, W, Cin), dconv)
+    drop_amax(out)
+    _call("dasr_conv3x3_dgrad_act_split2", _p(dconv), _p(dmax), _lib.ptr(ws[0], False, torch.float16), _p(ws[1]), _p(x_act),
+          _p(out), _p(amax, True), 1 if acc else 0, B, H, W, Cin, Cout, act, ps_r)
+    return set_amax(out, amax)
+
+
 # ---- the 9x9 output convolution in the same scheme (csrc/conv9_split.hip); w = the packed kernel (2,9,9,Cin,Cout) ------
 def conv9_split_supported(H, W, Cin, Cout):
     return bool(_lib.get().dasr_conv9_split_supported(H, W, Cin, Cout))

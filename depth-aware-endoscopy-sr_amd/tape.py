@@ -12,7 +12,7 @@ from . import ops
 class Var:
     """A device tensor plus its gradient slot."""
     __slots__ = ("data", "grad", "requires_grad", "name", "uses", "epilogue", "grad_is_preact", "event",
-                 "grad_event", "stats", "split", "amax", "pack", "epilogue_split")
+                 "grad_event", "stats", "split", "amax", "pack", "epilogue_split", "act_rec", "grads_in")
 
     def __init__(self, data, requires_grad=False, name=None):
         self.data = data
@@ -22,7 +22,9 @@ class Var:
         self.uses = 0                # differentiable consumers recorded during the forward
         self.epilogue = None         # (act, ps_r) when produced by a conv with a fused activation / PixelShuffle
         self.epilogue_split = False  # ... and that conv runs on the fp16 x 2 split kernels (its gradients want max |dconv|)
-        self.grad_is_preact = False  # the consumer already applied the epilogue backward (dasr_conv2d_dgrad_act, dasr_conv9_dgrad_act_split2)
+        self.act_rec = None          # (act, ps_r) of the producing conv's epilogue, residual layers included (graph.FUSE_SPLIT_DGRAD_ACT)
+        self.grads_in = 0            # gradient contributions received so far in this backward (compared with .uses)
+        self.grad_is_preact = False  # the consumer already applied the epilogue backward (dasr_conv2d_dgrad_act, dasr_conv9_dgrad_act_split2, dasr_conv3x3_dgrad_act_split2)
         self.event = None            # HIP event after the producing kernel when it ran on another stream
         self.grad_event = None       # HIP event after the kernel that produced .grad on another stream
         self.stats = None            # (mean, var) per (b, c) when the producing conv computed them in its epilogue
@@ -103,6 +105,7 @@ def accum(var, g, owned=True):
     consumer, so the first assignment must take a private copy before anyone adds into it."""
     if var is None or not var.requires_grad or g is None:
         return
+    var.grads_in += 1
     if var.grad is None:
         if owned:
             var.grad = g

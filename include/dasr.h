@@ -223,6 +223,17 @@ int dasr_conv3x3_dgrad_split2(const float* dconv, const float* dmax, const unsig
 int dasr_conv3x3_wgrad_split2(const float* x, const float* xmax, const float* dconv, const float* dmax, float* dw_hwio,
                               float* dbias, void* workspace, size_t workspace_bytes, int B, int H, int W, int Cin, int Cout,
                               void* stream);
+/* dasr_conv3x3_dgrad_split2 with the PRODUCER's epilogue backward in its own epilogue, for Cin == 32 (the kernel that produces
+ * 32 channels: the HR tail).  x_act [B,H,W,Cin] = this convolution's saved input = the producer's output behind its
+ * activation `act` (none / ReLU / LeakyReLU(0.2)) and, with ps_r == 2, its PixelShuffle(2).
+ *   ps_r == 1: dprev [B,H,W,Cin] = (dx (+ the old dprev if accumulate)) * act'(x_act) - the derivative applies to the SUM
+ *   ps_r == 2: dprev [B,H/2,W/2,4 Cin], dprev[..][4c + 2(y&1) + (x&1)] = dx[y][x][c] * act'(x_act[y][x][c]); H, W even, no accumulate
+ * Bit for bit what dasr_conv2d_epilogue_bwd makes of dasr_conv3x3_dgrad_split2's result, without the pass over it.
+ * dprev_amax (may be NULL): amax buffer for max |dprev|.  DASR_E_UNSUPPORTED where dasr_conv3x3_dgrad_act_supported() is 0. */
+int dasr_conv3x3_dgrad_act_supported(int H, int W, int Cin, int Cout, int act, int ps_r, int accumulate);
+int dasr_conv3x3_dgrad_act_split2(const float* dconv, const float* dmax, const unsigned short* w_split, const float* wmax,
+                                  const float* x_act, float* dprev, float* dprev_amax, int accumulate, int B, int H, int W,
+                                  int Cin, int Cout, int act, int ps_r, void* stream);
 
 /* The 9x9 output convolution (conv_output, sftmd_arch.py:910,948: Cin % 32 == 0 -> Cout <= 3, pad 4) in the same fp16 x 2
  * scheme (csrc/conv9_split.hip): fp32 x / w / y / dy / dx / dw, operands split into two scaled fp16 pieces when they are
