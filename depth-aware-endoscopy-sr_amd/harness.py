@@ -7,7 +7,9 @@ weights, codes/models/modules/mask_loss.py:44-90), Adam(lr 1e-3, betas (0.9, 0.9
 generator's parameters plus the loss weights, CosineAnnealingLR_Restart stepped BEFORE the optimiser
 (codes/models/lr_scheduler.py:34-62).  Losses and optimiser stay PyTorch (north_star); the generator
 forward/backward is the HIP path, and so are the sums both losses need (``fused_losses``: one pass over sr / hr for one-hot
-masks and for soft masks alike; the division, the softmax weighting and the collective stay in PyTorch).
+masks and for soft masks alike; the division, the softmax weighting and the collective stay in PyTorch).  The reference's
+optional SSIM criterion (``Trainer(ssim_weight=...)``, off by default as in the shipped ymls) is ``SSIMLoss``: ``dasr_ssim``
+forward, ``dasr_ssim_bwd`` backward, in the fused losses' autograd node and collective when both are on.
 
 Data parallel: one process per GPU (torchrun), ``torch.distributed`` backend ``nccl`` (= RCCL over
 xGMI) on the GPU box, ``gloo`` in CPU tests.  The net itself is communication-free (instance norm is
@@ -82,12 +84,108 @@ class _RegionSumsSoft(torch.autograd.Function):
         return ops.loss_bwd_soft(sr, hr, mask, dsums.contiguous(), ctx.K), None, None, None
 
 
-def fused_losses(sr, hr, mask_list, trainable_weight, pixel_weight, dynamic_weight, group=None):
+def ssim_torch(img1, img2):
+    """The PyTorch formulation of the reference's ``SSIM()`` criterion (models/modules/ssim_loss.py:7-37, size_average=True):
+    the 2-D window g g^T formed in fp32, five grouped convolutions, the SSIM map and its mean.  What ``SSIMLoss`` computes
+    for tensors the HIP kernels do not take (CPU, other dtypes, other layouts)."""
+    from .validate import _window_1d
+    g = _window_1d().unsqueeze(1)
+    ch = img1.shape[1]
+    window = g.mm(g.t()).float().unsqueeze(0).unsqueeze(0).expand(ch, 1, 11, 11).contiguous().to(img1.device).type_as(img1)
+    mu1 = F.conv2d(img1, window, padding=5, groups=ch)
+    mu2 = F.conv2d(img2, window, padding=5, groups=ch)
+    mu1_sq, mu2_sq, mu1_mu2 = mu1.pow(2), mu2.pow(2), mu1 * mu2
+    sigma1_sq = F.conv2d(img1 * img1, window, padding=5, groups=ch) - mu1_sq
+    sigma2_sq = F.conv2d(img2 * img2, window, padding=5, groups=ch) - mu2_sq
+    sigma12 = F.conv2d(img1 * img2, window, padding=5, groups=ch) - mu1_mu2
+    C1, C2 = 0.01 ** 2, 0.03 ** 2
+    return (((2 * mu1_mu2 + C1) * (2 * sigma12 + C2)) / ((mu1_sq + mu2_sq + C1) * (sigma1_sq + sigma2_sq + C2))).mean()
+
+
+def _dscale(dS):
+    """dL/dS as the one-element device tensor dasr_ssim_bwd reads (no host read-back)."""
+    return dS.reshape(1).to(torch.float32).contiguous()
+
+
+class _SSIM(torch.autograd.Function):
+    """S = mean of the SSIM map (dasr_ssim; nothing saved but the two images); backward: dasr_ssim_bwd, one launch.
+    Gradient to the first image only."""
+
+    @staticmethod
+    def forward(ctx, img1, img2):
+        from . import ops
+        ctx.save_for_backward(img1, img2)
+        return ops.ssim(img1, img2).mean()
+
+    @staticmethod
+    def backward(ctx, dS):
+        from . import ops
+        img1, img2 = ctx.saved_tensors
+        return ops.ssim_bwd(img1, img2, _dscale(dS)), None
+
+
+class _RegionSumsSSIM(torch.autograd.Function):
+    """(_RegionSums or _RegionSumsSoft, _SSIM) as ONE node: the 9x9 dgrad takes dL/dsr as one tensor, so the SSIM backward
+    adds into the dsr the loss backward has just written (dasr_ssim_bwd, accumulate) instead of autograd adding two
+    HR-sized tensors in a pass of its own.  ``aux``: region bytes (``soft`` False) or float masks (``soft`` True)."""
+
+    @staticmethod
+    def forward(ctx, sr, hr, aux, K, soft):
+        from . import ops
+        sr_c, hr_c = sr.contiguous(), hr.contiguous()
+        aux = aux.detach().contiguous() if soft else aux
+        ctx.save_for_backward(sr_c, hr_c, aux)
+        ctx.K, ctx.soft = K, soft
+        sums = (ops.loss_sums_soft if soft else ops.loss_sums)(sr_c, hr_c, aux, K)
+        return sums, ops.ssim(sr_c, hr_c).mean()
+
+    @staticmethod
+    def backward(ctx, dsums, dS):
+        from . import ops
+        sr, hr, aux = ctx.saved_tensors
+        dsr = (ops.loss_bwd_soft if ctx.soft else ops.loss_bwd)(sr, hr, aux, dsums.contiguous(), ctx.K)
+        ops.ssim_bwd(sr, hr, _dscale(dS), out=dsr, accumulate=True)
+        return dsr, None, None, None, None
+
+
+class SSIMLoss(torch.nn.Module):
+    """The reference's ``SSIM()`` criterion (models/modules/ssim_loss.py:39-63, ``size_average=True``): the mean of the SSIM
+    map of two [B,C,H,W] images, 11 x 11 Gaussian windows.  fp32 contiguous CUDA tensors go through the HIP kernels
+    (dasr_ssim forward, dasr_ssim_bwd backward: one launch each, nothing saved between them); anything else through the
+    PyTorch formulation (``ssim_torch``).  The gradient goes to the FIRST image only: a second image that requires a
+    gradient is refused."""
+
+    force_torch = False          # tests: compare the kernels against the PyTorch formulation on the same tensors
+
+    def __init__(self, window_size=11, size_average=True):
+        super().__init__()
+        if window_size != 11 or not size_average:
+            raise NotImplementedError("SSIMLoss: the reference's configuration only (11 x 11 window, size_average=True)")
+
+    @classmethod
+    def hip_ok(cls, img1, img2):
+        if cls.force_torch or img1.dim() != 4 or img1.shape != img2.shape or img1.shape[0] * img1.shape[1] > 65535:
+            return False
+        return all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in (img1, img2))
+
+    def forward(self, img1, img2):
+        if img2.requires_grad:
+            raise ValueError("SSIMLoss: the second image must not require a gradient (the criterion differentiates "
+                             "with respect to the first image only)")
+        if self.hip_ok(img1, img2):
+            return _SSIM.apply(img1, img2)
+        return ssim_torch(img1, img2)
+
+
+def fused_losses(sr, hr, mask_list, trainable_weight, pixel_weight, dynamic_weight, group=None, with_ssim=False):
     """l_pix and l_dynamic from one pass over (sr, hr) on the GPU: the region-byte kernels when the masks are one-hot, the
     soft-mask kernels when they are not (contiguous fp32 CUDA masks of at most 16 regions that need no gradient), or None
     for anything else (the caller then uses the PyTorch formulation; that includes every mask tensor of more than 16
     regions, one-hot or not, which dasr_mask_compress used to reject with an error from here).  Same values and gradients as nn.L1Loss +
-    dynamic_weight_mask_loss('smoothl1'); with a process group the region sums are made global first."""
+    dynamic_weight_mask_loss('smoothl1'); with a process group the region sums are made global first.
+    ``with_ssim`` (the caller has checked ``SSIMLoss.hip_ok(sr, hr)``): the SSIM criterion of (sr, hr) rides along - in
+    the same autograd node, and its value in the same collective - and the result has two more entries: S with its
+    gradient, and its detached global value (the mean of the ranks' means: every rank's batch has the same size)."""
     from . import ops
     if not sr.is_cuda or sr.dtype != torch.float32 or mask_list.shape[2] == 0:
         return None
@@ -99,29 +197,42 @@ def fused_losses(sr, hr, mask_list, trainable_weight, pixel_weight, dynamic_weig
     K = mask_list.shape[1]
     if K > ops.LOSS_MAX_REGIONS:              # beyond the kernels (and beyond dasr_mask_compress): nothing to classify
         return None
+    S = None
     if prep.attach_region(mask_list):         # no-op for masks from prep.depth_to_masks / already classified
-        sums = _RegionSums.apply(sr, hr, graph.attached_region(mask_list), K)
+        if with_ssim:
+            sums, S = _RegionSumsSSIM.apply(sr, hr, graph.attached_region(mask_list), K, False)
+        else:
+            sums = _RegionSums.apply(sr, hr, graph.attached_region(mask_list), K)
     elif (mask_list.is_cuda and mask_list.dtype == torch.float32 and mask_list.is_contiguous()
           and not mask_list.requires_grad):
-        sums = _RegionSumsSoft.apply(sr, hr, mask_list, K)
+        if with_ssim:
+            sums, S = _RegionSumsSSIM.apply(sr, hr, mask_list, K, True)
+        else:
+            sums = _RegionSumsSoft.apply(sr, hr, mask_list, K)
     else:
         return None
     num, den, l1 = sums[:K], sums[K:2 * K].detach(), sums[2 * K]
     world = _world(group)
     l_pix = pixel_weight * l1 / sr.numel()
     l_pix_global = l_pix.detach()
+    S_global = S.detach() if with_ssim else None
     if world > 1:
         # ONE collective for everything the step needs from the other ranks' losses: K numerators | K denominators | L1 sum
-        g = sums.detach().clone()
+        # (| S when the SSIM criterion is on)
+        g = torch.cat([sums.detach(), S.detach().reshape(1)]) if with_ssim else sums.detach().clone()
         torch.distributed.all_reduce(g, group=group)
         gnum, gden = g[:K], g[K:2 * K]
         local = num / gden * world
         per = gnum / gden + (local - local.detach())
         l_pix_global = pixel_weight * g[2 * K] / (sr.numel() * world)
+        if with_ssim:
+            S_global = g[2 * K + 1] / world
     else:
         per = num / den
     sm = F.softmax(trainable_weight, dim=0)
     l_dyn = (sm * per).sum() * dynamic_weight
+    if with_ssim:
+        return l_pix, l_dyn, per, sm, l_pix_global, S, S_global
     return l_pix, l_dyn, per, sm, l_pix_global
 
 
@@ -138,8 +249,9 @@ class DynamicMaskLoss(torch.nn.Module):
         self.trainable_weight = torch.nn.Parameter(torch.ones(num_regions))
 
     def forward(self, sr, hr, mask_list, group=None, piggyback=None):
-        """``piggyback``: a detached scalar summed over the ranks in the same collective as the region sums (the
-        harness passes its local L1 value); its global sum is left in ``self.piggyback_sum``."""
+        """``piggyback``: a detached scalar (or small vector) summed over the ranks in the same collective as the region
+        sums (the harness passes its local L1 value, and the SSIM value beside it when that criterion is on); its global
+        sum is left in ``self.piggyback_sum``, in the same shape."""
         K = mask_list.shape[1]
         assert K == self.trainable_weight.numel(), "dynamic loss: %d trainable region weights but %d mask channels" % (self.trainable_weight.numel(), K)
         sm = F.softmax(self.trainable_weight, dim=0)
@@ -153,12 +265,12 @@ class DynamicMaskLoss(torch.nn.Module):
         world = _world(group)
         self.piggyback_sum = piggyback
         if world > 1:
-            parts = [num.detach(), den.detach()] + ([piggyback.detach().reshape(1)] if piggyback is not None else [])
+            parts = [num.detach(), den.detach()] + ([piggyback.detach().reshape(-1)] if piggyback is not None else [])
             g = torch.cat(parts)
             torch.distributed.all_reduce(g, group=group)          # one collective: numerators | denominators | piggyback
             gnum, gden = g[:K], g[K:2 * K]
             if piggyback is not None:
-                self.piggyback_sum = g[2 * K]
+                self.piggyback_sum = g[2 * K] if piggyback.dim() == 0 else g[2 * K:]
             # value = global ratio; gradient: this rank's numerator over the global denominator, times world so
             # that the later gradient AVERAGE over ranks equals the gradient of the global loss
             local = num / gden * world
@@ -175,8 +287,16 @@ class Trainer:
 
     def __init__(self, net, num_regions=10, lr=1e-3, betas=(0.9, 0.99), weight_decay=0.0, pixel_weight=1.0,
                  dynamic_weight=10.0, group=None, T_period=(20000,) * 4, restarts=(20000, 40000, 60000),
-                 restart_weights=(1, 1, 1), eta_min=1e-7, use_graph=False):
-        """``use_graph``: capture the whole step (zero_grad, forward, losses, backward, Adam) into ONE hipGraph after three
+                 restart_weights=(1, 1, 1), eta_min=1e-7, use_graph=False, ssim_weight=None):
+        """``ssim_weight``: None (the default) leaves the SSIM criterion off - the step, its launches and its log are those
+        of a Trainer without the argument.  A number w switches it on as the reference does
+        (``train.ssim_loss.use_ssim_criterion`` / ``ssim_weight``; F_model_depthCond.py:71-75,177-180):
+        ``total += w * SSIM(sr, gt)`` - the SIMILARITY itself is added, so it takes a NEGATIVE weight to maximise it - and
+        the log gains ``l_ssim`` (the weighted term, which ``l_all`` includes; with a process group the global value).  On
+        the GPU the term is ``dasr_ssim`` forward and ``dasr_ssim_bwd`` backward, adding into the loss kernels' dL/dsr;
+        under ``use_graph`` it is captured with the rest of the step.
+
+        ``use_graph``: capture the whole step (zero_grad, forward, losses, backward, Adam) into ONE hipGraph after three
         eager steps and replay it afterwards - for steps whose ~2000 launches cost the host more than the GPU needs to run
         them (x8 / 16 frames / bf16: 22-30 ms of enqueue for a 35 ms step).  Single-rank only (the gradient exchange stays
         eager); same-shaped inputs (the loader's tensors are copied into the captured ones); Adam runs in its
@@ -192,6 +312,8 @@ class Trainer:
         device = next(net.parameters()).device
         self.dynamic_loss = DynamicMaskLoss(num_regions, dynamic_weight).to(device)
         self.l_pix_w = pixel_weight
+        self.l_ssim_w = None if ssim_weight is None else float(ssim_weight)
+        self.ssim_loss = None if ssim_weight is None else SSIMLoss()
         self.params = [p for p in net.parameters() if p.requires_grad] + list(self.dynamic_loss.parameters())
         self.base_lr = lr
         self.use_graph = bool(use_graph) and device.type == "cuda" and self.world == 1
@@ -338,21 +460,51 @@ class Trainer:
             prep.attach_region(masks)          # before the step's work is queued; free for prep.depth_to_masks output
         sr = self.net(lq, depth, masks)
         grp = self.group if self.world > 1 else None
-        fused = fused_losses(sr, gt, masks, self.dynamic_loss.trainable_weight, self.l_pix_w,
-                             self.dynamic_loss.l_mask_w, grp)
-        if fused is not None:
-            l_pix, l_dyn, per, sm, l_pix_log = fused
-        else:
-            l_pix = self.l_pix_w * F.l1_loss(sr, gt)
-            per, weighted, l_dyn, sm = self.dynamic_loss(sr, gt, masks, grp, piggyback=l_pix.detach())
-            l_pix_log = self.dynamic_loss.piggyback_sum / self.world     # the global-batch value
+        l_pix, l_dyn, l_pix_log, S, S_log = self._losses(sr, gt, masks, grp)
         total = l_pix + l_dyn
+        if S is not None:
+            total = total + self.l_ssim_w * S
         self._buckets, self._submitted = [], set()
         total.backward()
         self._finish_allreduce()
         self.optimizer.step()
         self.log = {"l_all": l_pix_log + l_dyn.detach(), "l_pix": l_pix_log, "l_dynamic": l_dyn.detach()}
+        if S is not None:
+            l_ssim = self.l_ssim_w * S_log
+            self.log["l_all"] = self.log["l_all"] + l_ssim
+            self.log["l_ssim"] = l_ssim
         return self.log
+
+    def _losses(self, sr, gt, masks, grp):
+        """``(l_pix, l_dyn, l_pix_log, S, S_log)`` of a step: the loss terms with their gradients, the global-batch L1
+        value for the log, and - None, None with the SSIM criterion off - S with its gradient and its global value.  On the
+        HIP path S shares the fused losses' autograd node and collective; otherwise it is a term of its own (``SSIMLoss``)
+        whose value rides with the L1 value in the dynamic loss's collective."""
+        on = self.ssim_loss is not None
+        hip = on and self.ssim_loss.hip_ok(sr, gt)
+        fused = fused_losses(sr, gt, masks, self.dynamic_loss.trainable_weight, self.l_pix_w, self.dynamic_loss.l_mask_w,
+                             grp, **({"with_ssim": True} if hip else {}))
+        S = S_log = None
+        if fused is not None:
+            l_pix, l_dyn, l_pix_log = fused[0], fused[1], fused[4]
+            if hip:
+                S, S_log = fused[5], fused[6]
+            elif on:                                # (sr the kernels do not take, masks they do: a collective of its own)
+                S = self.ssim_loss(sr, gt)
+                S_log = S.detach()
+                if self.world > 1:
+                    S_log = S_log.clone()
+                    torch.distributed.all_reduce(S_log, group=grp)
+                    S_log = S_log / self.world
+            return l_pix, l_dyn, l_pix_log, S, S_log
+        l_pix = self.l_pix_w * F.l1_loss(sr, gt)
+        if on:
+            S = self.ssim_loss(sr, gt)
+        piggyback = l_pix.detach() if S is None else torch.stack([l_pix.detach(), S.detach()])
+        per, weighted, l_dyn, sm = self.dynamic_loss(sr, gt, masks, grp, piggyback=piggyback)
+        glob = self.dynamic_loss.piggyback_sum / self.world              # the global-batch values
+        l_pix_log, S_log = (glob, None) if S is None else glob.unbind(0)
+        return l_pix, l_dyn, l_pix_log, S, S_log
 
     @torch.no_grad()
     def test(self, lq, depth, masks):

@@ -27,6 +27,13 @@ def define_G(opt):
                     ablate_depth_matrix=bool(g('ablate_depth_matrix', False)))
 
 
+def ssim_weight(opt):
+    """``harness.Trainer(ssim_weight=...)`` from an option tree: ``train.ssim_loss.ssim_weight`` when
+    ``train.ssim_loss.use_ssim_criterion`` is set (F_model_depthCond.py:71-75), else None (every shipped yml)."""
+    o = (opt.get('train') or {}).get('ssim_loss') or {}
+    return float(o['ssim_weight']) if o.get('use_ssim_criterion') else None
+
+
 X8_NETWORK_G = dict(which_model_G='DepthNet', which_ResBlk_depth=list(range(14)), in_nc=3, out_nc=3, nf=64, nb=16,
                     upscale=8, code_length=10, depth_latent_ch=256, norm_type='weight_norm',
                     use_trainable_params=True, norm_gamma=0.1, norm_beta=0.1, ablate_depth_block=False,

@@ -860,6 +860,44 @@ def loss_bwd_soft(sr, hr, mask, dsums, K):
     return dsr
 
 
+# ---- SSIM: validation metric and training criterion (csrc/ssim.hip, csrc/ssim_bwd.hip) ----------
+_ssim_window = None
+
+
+def _ssim_window11():
+    """The reference's eleven 1-D window weights as a host array (the entry points take them by value)."""
+    global _ssim_window
+    if _ssim_window is None:
+        from .validate import _window_1d
+        _ssim_window = (ctypes.c_float * 11)(*[float(v) for v in _window_1d()])
+    return ctypes.cast(_ssim_window, ctypes.c_void_p)
+
+
+def ssim(img1, img2):
+    """Per-sample mean of the SSIM map of two [B,C,H,W] images (dasr_ssim): float32 [B]."""
+    a, b = img1.contiguous().float(), img2.contiguous().float()
+    B, C, H, W = a.shape
+    out = torch.empty((B,), dtype=torch.float32, device=a.device)
+    nbytes = int(_lib.get().dasr_ssim_workspace(B, C, H, W))
+    ws = torch.empty((max(1, nbytes // 4),), dtype=torch.float32, device=a.device)
+    _call("dasr_ssim", _p(a), _p(b), _ssim_window11(), _p(out), _p(ws), nbytes, B, C, H, W)
+    return out
+
+
+def ssim_bwd(img1, img2, dscale, out=None, accumulate=False):
+    """dscale * dS/dimg1 for S = the mean of the SSIM map over all of [B,C,H,W] (dasr_ssim_bwd, one launch).  ``dscale``:
+    a float32 tensor of one element on the images' device (never read by the host).  ``out``: the buffer to write, or with
+    ``accumulate`` to add into; a new one by default."""
+    B, C, H, W = img1.shape
+    assert img2.shape == img1.shape and dscale.numel() == 1
+    if out is None:
+        assert not accumulate, "ssim_bwd: accumulate needs the buffer to add into"
+        out = torch.empty_like(img1)
+    assert out.shape == img1.shape
+    _call("dasr_ssim_bwd", _p(img1), _p(img2), _ssim_window11(), _p(dscale), _p(out), int(bool(accumulate)), B, C, H, W)
+    return out
+
+
 # ---- video frames: the uint8 edge of inference (csrc/frame.hip) --------------------------------
 def _pu8(t):
     return _lib.ptr(t, dtype=torch.uint8)

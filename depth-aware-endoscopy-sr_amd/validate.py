@@ -47,17 +47,10 @@ def ssim(img1, img2, window_size=11, size_average=True):
     """pytorch_ssim.ssim (pytorch_ssim/__init__.py:17-37,65-73): 11x11 Gaussian (sigma 1.5) windows, zero padding,
     C1 = 0.01^2, C2 = 0.03^2 on [0,1] images `[B,C,H,W]` - one HIP kernel pass over both images (dasr_ssim: the five
     windowed moments, the SSIM ratio and its mean), no torch compute ops."""
-    import ctypes
-    from . import _lib, ops
+    from . import ops
     if window_size != 11:
         raise NotImplementedError("dasr_amd.validate.ssim: the reference's 11 x 11 window only")
-    a, b = img1.contiguous().float(), img2.contiguous().float()
-    B, C, H, W = a.shape
-    out = torch.empty((B,), dtype=torch.float32, device=a.device)
-    nbytes = int(_lib.get().dasr_ssim_workspace(B, C, H, W))
-    ws = torch.empty((max(1, nbytes // 4),), dtype=torch.float32, device=a.device)
-    g = (ctypes.c_float * 11)(*[float(v) for v in _window_1d()])
-    ops._call("dasr_ssim", ops._p(a), ops._p(b), ctypes.cast(g, ctypes.c_void_p), ops._p(out), ops._p(ws), nbytes, B, C, H, W)
+    out = ops.ssim(img1, img2)
     return out.mean() if size_average else out
 
 

@@ -491,6 +491,13 @@ int dasr_weight_collapse_t2(const float* dw_expanded, const float* dbias_expande
 size_t dasr_ssim_workspace(int B, int C, int H, int W);
 int dasr_ssim(const float* img1, const float* img2, const float* window11, float* out_per_sample, void* workspace,
               size_t workspace_bytes, int B, int C, int H, int W, void* stream);
+/* The same quantity as a training criterion (models/modules/ssim_loss.py, F_model_depthCond.py:179): with
+ * S = mean over (B,C,H,W) of the SSIM map, dimg1 (=|+=) dscale[0] * dS/dimg1, in one launch that reads img1, img2 and
+ * writes dimg1 - nothing is saved by dasr_ssim for it (csrc/ssim_bwd.hip).  No gradient to img2.  dscale: DEVICE pointer to
+ * one float (dL/dS), read by the kernel: no host read-back, the call can be captured.  accumulate != 0 adds into dimg1
+ * (every element is written by exactly one thread), 0 overwrites.  window11: HOST pointer as above. */
+int dasr_ssim_bwd(const float* img1, const float* img2, const float* window11, const float* dscale, float* dimg1,
+                  int accumulate, int B, int C, int H, int W, void* stream);
 
 /* ---- video frames: the uint8 edge of inference (csrc/frame.hip) ----------------------------------------------------
  * A camera frame is uint8 HWC (BGR as cv2 delivers it); the network is NHWC inside.  These three keep the host out of the
