@@ -9,7 +9,10 @@ generator's parameters plus the loss weights, CosineAnnealingLR_Restart stepped 
 forward/backward is the HIP path, and so are the sums both losses need (``fused_losses``: one pass over sr / hr for one-hot
 masks and for soft masks alike; the division, the softmax weighting and the collective stay in PyTorch).  The reference's
 optional SSIM criterion (``Trainer(ssim_weight=...)``, off by default as in the shipped ymls) is ``SSIMLoss``: ``dasr_ssim``
-forward, ``dasr_ssim_bwd`` backward, in the fused losses' autograd node and collective when both are on.
+forward, ``dasr_ssim_bwd`` backward, in the fused losses' autograd node and collective when both are on.  The other criteria
+a reference yml can name - ``pixel_criterion`` l1 / l2 / cb, ``dynamic_criterion`` l1 / l2 / smoothl1, the dynamic term off,
+the static ``mask_loss`` - are ``Trainer`` arguments too (``networks.criteria(opt)``); any combination but the default goes
+through ``criterion_losses``: one ``dasr_loss_sums[_soft]_crit`` pass forward, one ``dasr_loss_bwd[_soft]_crit`` backward.
 
 Data parallel: one process per GPU (torchrun), ``torch.distributed`` backend ``nccl`` (= RCCL over
 xGMI) on the GPU box, ``gloo`` in CPU tests.  The net itself is communication-free (instance norm is
@@ -236,6 +239,192 @@ def fused_losses(sr, hr, mask_list, trainable_weight, pixel_weight, dynamic_weig
     return l_pix, l_dyn, per, sm, l_pix_global
 
 
+PIXEL_CRITERIA = ("l1", "l2", "cb")               # train.pixel_criterion (F_model_depthCond.py:50-58)
+REGION_CRITERIA = ("l1", "l2", "smoothl1")        # dynamic_loss.dynamic_criterion / mask_loss.mask_criterion (mask_loss.py)
+CB_EPS = 1e-6                                     # CharbonnierLoss(eps) (loss.py:40)
+
+
+def check_criteria(pixel_criterion, dynamic_criterion, mask_criterion):
+    """The reference's own refusals: an unknown name is NotImplementedError there too, and 'cb' as a REGION criterion dies
+    with a NameError (mask_loss.py never imports CharbonnierLoss), so it is refused here with the reason."""
+    if pixel_criterion not in PIXEL_CRITERIA:
+        raise NotImplementedError("Loss type [%s] is not recognized." % (pixel_criterion,))
+    for what, c in (("dynamic_criterion", dynamic_criterion), ("mask_criterion", mask_criterion)):
+        if c == "cb":
+            raise NotImplementedError("%s='cb': the reference's mask_loss.py names CharbonnierLoss without importing it "
+                                      "(a NameError there), so there is no behaviour to reproduce; use l1, l2 or smoothl1"
+                                      % what)
+        if c is not None and c not in REGION_CRITERIA:
+            raise NotImplementedError("Loss type [%s] for depth loss is not recognized." % (c,))
+
+
+class _CritSums(torch.autograd.Function):
+    """sums = (K numerators of criterion A | K areas | pixel-criterion sum [| K numerators of criterion B]) in ONE pass over
+    sr, hr (dasr_loss_sums_crit / dasr_loss_sums_soft_crit) and one elementwise backward (dasr_loss_bwd[_soft]_crit).
+    ``aux``: region bytes (uint8) or float masks; ``crits`` = (pixel, A, B or None).  ``with_ssim``: a second output, the
+    SSIM criterion of (sr, hr), whose backward adds into the same dsr (as in _RegionSumsSSIM)."""
+
+    @staticmethod
+    def forward(ctx, sr, hr, aux, K, crits, with_ssim):
+        from . import ops
+        sr_c, hr_c = sr.contiguous(), hr.contiguous()
+        if aux.dtype != torch.uint8:
+            aux = aux.detach().contiguous()
+        ctx.save_for_backward(sr_c, hr_c, aux)
+        ctx.K, ctx.crits, ctx.with_ssim = K, crits, with_ssim
+        sums = ops.loss_sums_crit(sr_c, hr_c, aux, K, *crits)
+        if with_ssim:
+            return sums, ops.ssim(sr_c, hr_c).mean()
+        return sums
+
+    @staticmethod
+    def backward(ctx, dsums, dS=None):
+        from . import ops
+        sr, hr, aux = ctx.saved_tensors
+        dsr = ops.loss_bwd_crit(sr, hr, aux, dsums.contiguous(), ctx.K, *ctx.crits)
+        if ctx.with_ssim:
+            ops.ssim_bwd(sr, hr, _dscale(dS), out=dsr, accumulate=True)
+        return dsr, None, None, None, None, None
+
+
+def _pixel_sum(d, pixel_criterion):
+    if pixel_criterion == "l1":
+        return d.abs().sum()
+    if pixel_criterion == "l2":
+        return (d * d).sum()
+    return torch.sqrt(d * d + CB_EPS).sum()
+
+
+def _region_sum(u, criterion):
+    if criterion == "l1":
+        return u.abs().sum()
+    if criterion == "l2":
+        return (u * u).sum()
+    return F.smooth_l1_loss(u, torch.zeros_like(u), reduction="sum")
+
+
+def criterion_sums_torch(sr, hr, mask_list, pixel_criterion, crit_a, crit_b=None):
+    """The PyTorch formulation of what the ``_crit`` kernels sum, in their layout (K numerators of A | K areas | pixel sum
+    [| K numerators of B]) and differentiable by autograd (the masks included): one masked pass per region, as the reference
+    makes them.  ``crit_a`` None: the pixel sum alone."""
+    d = sr - hr
+    px = _pixel_sum(d, pixel_criterion).reshape(1)
+    if crit_a is None:
+        return px
+    na, area, nb = [], [], []
+    for k in range(mask_list.shape[1]):
+        m = F.interpolate(mask_list[:, k:k + 1], size=sr.shape[2:], mode="nearest")
+        u = m * d
+        na.append(_region_sum(u, crit_a))
+        area.append(float(sr.shape[1]) * m.sum())
+        if crit_b is not None:
+            nb.append(_region_sum(u, crit_b))
+    return torch.cat([torch.stack(na), torch.stack(area), px] + ([torch.stack(nb)] if crit_b is not None else []))
+
+
+def _criterion_aux(sr, mask_list):
+    """What the ``_crit`` kernels read beside sr / hr - region bytes for one-hot masks, the masks themselves when they are
+    soft - or None where ``fused_losses`` would return None (CPU tensors, more than 16 regions, masks that need a gradient,
+    HR / LR sizes that are no integer scale)."""
+    from . import graph, ops, prep
+    if not sr.is_cuda or sr.dtype != torch.float32 or mask_list.shape[2] == 0:
+        return None
+    H, W = sr.shape[2:]
+    h, w = mask_list.shape[2:]
+    if H % h or W % w or H // h != W // w or mask_list.shape[1] > ops.LOSS_MAX_REGIONS:
+        return None
+    if prep.attach_region(mask_list):
+        return graph.attached_region(mask_list)
+    if mask_list.is_cuda and mask_list.dtype == torch.float32 and mask_list.is_contiguous() and not mask_list.requires_grad:
+        return mask_list
+    return None
+
+
+def criterion_losses(sr, hr, mask_list, trainable_weight, pixel_weight=1.0, dynamic_weight=10.0, pixel_criterion="l1",
+                     dynamic_criterion="smoothl1", mask_criterion=None, mask_weight=1.0, mask_index=None, group=None,
+                     ssim=None, force_torch=False):
+    """The loss terms of a step for ANY combination of the reference's criteria (``fused_losses`` stays what the default
+    combination runs).  Values follow the reference, oddities included:
+
+    * pixel: 'l1' / 'l2' are means over all elements, 'cb' is the SUM of sqrt(d^2 + 1e-6) (loss.py:46), each times
+      ``pixel_weight``;
+    * a region criterion 'smoothl1' is the ratio sum smooth_l1(M_k d) / (C sum M_k); 'l1' / 'l2' are nn.L1Loss / nn.MSELoss
+      of the masked images, i.e. the mean over ALL B*C*H*W elements of |M_k d| or (M_k d)^2 - not a ratio to the area;
+    * dynamic term (``dynamic_weight`` None: off): ``dynamic_weight * sum_k softmax(trainable_weight)_k per_k``;
+    * static mask term (``mask_criterion`` None: off): ``mask_weight * per_k`` of the ONE region ``mask_index`` names (a
+      device int64 tensor of one element, picked on the device: no host read-back), taken from the K sums the pass produced
+      anyway; a second set of sums is computed only when ``mask_criterion != dynamic_criterion``.
+
+    Fused path (one ``_crit`` pass forward, one backward; the SSIM criterion ``ssim`` rides in the node when its kernels take
+    the tensors) under the rule of ``fused_losses``; otherwise - and with ``force_torch`` - ``criterion_sums_torch``.  With
+    both region terms off the pixel criterion is one PyTorch expression and no kernel runs.
+
+    More than one rank: ONE collective carries every sum (and S).  The logged pixel value is the global batch's; 'smoothl1'
+    in the dynamic term is the global ratio as in ``fused_losses``; 'l1' / 'l2' there need no denominators - the value is the
+    global mean, the gradient the local mean, which the gradient average over ranks makes global.  'cb' being a sum, its
+    gradient carrier is ``world *`` the local sum for the same reason.  The static mask term stays RANK-LOCAL: the
+    reference's ranks each draw their own region, so there is no global quantity to form.
+
+    Returns a dict: ``l_pix`` (with gradient), ``l_pix_log`` (global value), ``l_dyn`` / ``l_mask`` (None when off),
+    ``S`` / ``S_log`` (None without ``ssim``), ``per`` (the dynamic term's K values or None), ``fused`` (bool)."""
+    check_criteria(pixel_criterion, dynamic_criterion, mask_criterion)
+    dyn_on, mask_on = dynamic_weight is not None, mask_criterion is not None
+    crit_a = dynamic_criterion if dyn_on else mask_criterion
+    crit_b = mask_criterion if dyn_on and mask_on and mask_criterion != dynamic_criterion else None
+    K = mask_list.shape[1] if crit_a is not None else 0
+    N = sr.numel()
+    world = _world(group)
+    S = None
+    aux = None if force_torch or crit_a is None else _criterion_aux(sr, mask_list)
+    if aux is not None:
+        crits = (pixel_criterion, crit_a, crit_b)
+        if ssim is not None and ssim.hip_ok(sr, hr):
+            sums, S = _CritSums.apply(sr, hr, aux, K, crits, True)
+        else:
+            sums = _CritSums.apply(sr, hr, aux, K, crits, False)
+    else:
+        sums = criterion_sums_torch(sr, hr, mask_list, pixel_criterion, crit_a, crit_b)
+    if ssim is not None and S is None:
+        S = ssim(sr, hr)
+    g = sums.detach()
+    S_log = None if S is None else S.detach()
+    if world > 1:
+        g = torch.cat([g, S_log.reshape(1)]) if S is not None else g.clone()
+        torch.distributed.all_reduce(g, group=group)
+        if S is not None:
+            S_log = g[-1] / world
+    px, gpx = sums[2 * K], g[2 * K]
+    if pixel_criterion == "cb":
+        l_pix, l_pix_log = pixel_weight * px * world, pixel_weight * gpx
+    else:
+        l_pix, l_pix_log = pixel_weight * px / N, pixel_weight * gpx / (N * world)
+    den, gden = sums[K:2 * K].detach(), g[K:2 * K]
+
+    def per_region(num, gnum, criterion, local_only):
+        if criterion == "smoothl1":
+            if world > 1 and not local_only:
+                local = num / gden * world
+                return gnum / gden + (local - local.detach())
+            return num / den
+        if world > 1 and not local_only:
+            local = num / N
+            return gnum / (N * world) + (local - local.detach())
+        return num / N
+
+    out = dict(l_pix=l_pix, l_pix_log=l_pix_log.detach(), l_dyn=None, l_mask=None, per=None, S=S, S_log=S_log,
+               fused=aux is not None)
+    if dyn_on:
+        assert K == trainable_weight.numel(), "dynamic loss: %d trainable region weights but %d mask channels" % (trainable_weight.numel(), K)
+        per = per_region(sums[:K], g[:K], dynamic_criterion, False)
+        out["per"] = per
+        out["l_dyn"] = (F.softmax(trainable_weight, dim=0) * per).sum() * dynamic_weight
+    if mask_on:
+        lo = 2 * K + 1 if crit_b is not None else 0
+        per_m = per_region(sums[lo:lo + K], None, mask_criterion, True)
+        out["l_mask"] = mask_weight * per_m.index_select(0, mask_index).squeeze(0)
+    return out
+
+
 class DynamicMaskLoss(torch.nn.Module):
     """dynamic_weight_mask_loss with the 'smoothl1' criterion (mask_loss.py:44-90).
 
@@ -287,8 +476,25 @@ class Trainer:
 
     def __init__(self, net, num_regions=10, lr=1e-3, betas=(0.9, 0.99), weight_decay=0.0, pixel_weight=1.0,
                  dynamic_weight=10.0, group=None, T_period=(20000,) * 4, restarts=(20000, 40000, 60000),
-                 restart_weights=(1, 1, 1), eta_min=1e-7, use_graph=False, ssim_weight=None):
-        """``ssim_weight``: None (the default) leaves the SSIM criterion off - the step, its launches and its log are those
+                 restart_weights=(1, 1, 1), eta_min=1e-7, use_graph=False, ssim_weight=None, pixel_criterion="l1",
+                 dynamic_criterion="smoothl1", mask_criterion=None, mask_weight=1.0):
+        """``pixel_criterion`` ('l1' | 'l2' | 'cb'), ``dynamic_criterion`` ('l1' | 'l2' | 'smoothl1'), ``mask_criterion``
+        (None: off | 'l1' | 'l2' | 'smoothl1') with ``mask_weight``, and ``dynamic_weight=None`` (dynamic term off): the
+        ``train:`` switches of a reference yml (``networks.criteria(opt)`` maps one to these arguments;
+        F_model_depthCond.py:50-58,78-84,164,183-190, mask_loss.py).  With the defaults nothing about a step changes: its
+        launches, log keys, ``state_dict`` and captured graph are those of a Trainer without the arguments.  Any other
+        combination goes through ``criterion_losses`` (see there for the values, which follow the reference, oddities
+        included: 'cb' is a sum, 'l1' / 'l2' region losses are means over all elements): one ``_crit`` pass forward and one
+        backward on the GPU.  'cb' as a region criterion raises NotImplementedError.
+        The static mask loss draws ONE region per step as the reference does - ``np.random.randint(0, K, 1)[0]``
+        (mask_loss.py:24), so seeding ``np.random`` reproduces its sequence - and adds ``mask_weight *`` that region's value,
+        logged as ``l_mask`` and part of ``l_all``.  The drawn index lives in a device tensor that is refreshed before every
+        step (under ``use_graph`` before every replay, the way the learning rate is); ``self.mask_region`` keeps the host
+        copy.  With a process group the term stays RANK-LOCAL (value and log): the reference's ranks each draw their own
+        region.  With ``dynamic_weight=None`` there are no trainable loss weights - none in the optimizer, none in the saved
+        training state - and no ``l_dynamic`` in the log.
+
+        ``ssim_weight``: None (the default) leaves the SSIM criterion off - the step, its launches and its log are those
         of a Trainer without the argument.  A number w switches it on as the reference does
         (``train.ssim_loss.use_ssim_criterion`` / ``ssim_weight``; F_model_depthCond.py:71-75,177-180):
         ``total += w * SSIM(sr, gt)`` - the SIMILARITY itself is added, so it takes a NEGATIVE weight to maximise it - and
@@ -310,11 +516,21 @@ class Trainer:
         self.group = group
         self.world = _world(group)
         device = next(net.parameters()).device
-        self.dynamic_loss = DynamicMaskLoss(num_regions, dynamic_weight).to(device)
+        check_criteria(pixel_criterion, dynamic_criterion, mask_criterion)
+        self.pixel_criterion, self.dynamic_criterion, self.mask_criterion = pixel_criterion, dynamic_criterion, mask_criterion
+        self.l_mask_w = float(mask_weight)
+        # the default combination keeps the step it always had (_losses: fused_losses / DynamicMaskLoss)
+        self._default_criteria = (pixel_criterion == "l1" and dynamic_criterion == "smoothl1" and mask_criterion is None
+                                  and dynamic_weight is not None)
+        self.dynamic_loss = None if dynamic_weight is None else DynamicMaskLoss(num_regions, dynamic_weight).to(device)
+        self.mask_region = None
+        self._mask_idx = None if mask_criterion is None else torch.zeros(1, dtype=torch.int64, device=device)
         self.l_pix_w = pixel_weight
         self.l_ssim_w = None if ssim_weight is None else float(ssim_weight)
         self.ssim_loss = None if ssim_weight is None else SSIMLoss()
-        self.params = [p for p in net.parameters() if p.requires_grad] + list(self.dynamic_loss.parameters())
+        self.params = [p for p in net.parameters() if p.requires_grad]
+        if self.dynamic_loss is not None:
+            self.params += list(self.dynamic_loss.parameters())
         self.base_lr = lr
         self.use_graph = bool(use_graph) and device.type == "cuda" and self.world == 1
         self._graph = None
@@ -417,6 +633,7 @@ class Trainer:
             self._eager_steps += 1
             return self._eager_step(lq, gt, depth, masks)
         self.update_learning_rate()
+        self._draw_mask_region(masks)              # the captured step reads the tensor
         if self._graph is None:
             from . import prep
             # any host read-back happens before the capture, not inside it: the answer (region bytes, or the soft stamp)
@@ -451,7 +668,15 @@ class Trainer:
 
     def _eager_step(self, lq, gt, depth, masks):
         self.update_learning_rate()
+        self._draw_mask_region(masks)
         return self._step_body(lq, gt, depth, masks)
+
+    def _draw_mask_region(self, masks):
+        """The static mask loss's region of this step, drawn as mask_loss.py:24 draws it, into the device tensor."""
+        if self._mask_idx is not None:
+            import numpy as np
+            self.mask_region = int(np.random.randint(0, masks.shape[1], 1)[0])
+            self._mask_idx.fill_(self.mask_region)
 
     def _step_body(self, lq, gt, depth, masks):
         self.optimizer.zero_grad(set_to_none=True)
@@ -460,6 +685,8 @@ class Trainer:
             prep.attach_region(masks)          # before the step's work is queued; free for prep.depth_to_masks output
         sr = self.net(lq, depth, masks)
         grp = self.group if self.world > 1 else None
+        if not self._default_criteria:
+            return self._finish_step(self._criteria_terms(sr, gt, masks, grp))
         l_pix, l_dyn, l_pix_log, S, S_log = self._losses(sr, gt, masks, grp)
         total = l_pix + l_dyn
         if S is not None:
@@ -473,6 +700,37 @@ class Trainer:
             l_ssim = self.l_ssim_w * S_log
             self.log["l_all"] = self.log["l_all"] + l_ssim
             self.log["l_ssim"] = l_ssim
+        return self.log
+
+    force_torch_criteria = False  # tests: a non-default combination through the PyTorch formulation on the same tensors
+
+    def _criteria_terms(self, sr, gt, masks, grp):
+        dyn = self.dynamic_loss
+        return criterion_losses(sr, gt, masks, None if dyn is None else dyn.trainable_weight, self.l_pix_w,
+                                None if dyn is None else dyn.l_mask_w, self.pixel_criterion, self.dynamic_criterion,
+                                self.mask_criterion, self.l_mask_w, self._mask_idx, grp, self.ssim_loss,
+                                self.force_torch_criteria)
+
+    def _finish_step(self, t):
+        """Backward, gradient exchange, Adam and the log of a step whose terms ``criterion_losses`` computed: l_pix, then
+        l_ssim, l_mask and l_dynamic for the criteria that are on, in the reference's order (F_model_depthCond.py:163-190)."""
+        total = t["l_pix"]
+        log = {"l_pix": t["l_pix_log"]}
+        if t["S"] is not None:
+            total = total + self.l_ssim_w * t["S"]
+            log["l_ssim"] = self.l_ssim_w * t["S_log"]
+        if t["l_mask"] is not None:
+            total = total + t["l_mask"]
+            log["l_mask"] = t["l_mask"].detach()
+        if t["l_dyn"] is not None:
+            total = total + t["l_dyn"]
+            log["l_dynamic"] = t["l_dyn"].detach()
+        self._buckets, self._submitted = [], set()
+        total.backward()
+        self._finish_allreduce()
+        self.optimizer.step()
+        log["l_all"] = sum(log.values())
+        self.log = log
         return self.log
 
     def _losses(self, sr, gt, masks, grp):
@@ -536,8 +794,9 @@ def _save_training_state(trainer, path, epoch=0):
     the 10 dynamic-loss weights outside netG and does not checkpoint them at all."""
     state = {"epoch": epoch, "iter": trainer.step_count,
              "schedulers": [dict(last_epoch=trainer.step_count, base_lr=trainer.base_lr, **trainer.sched)],
-             "optimizers": [trainer.optimizer.state_dict()],
-             "loss_weights": trainer.dynamic_loss.trainable_weight.detach().cpu()}
+             "optimizers": [trainer.optimizer.state_dict()]}
+    if trainer.dynamic_loss is not None:           # (dynamic_weight=None: no trainable loss weights to keep)
+        state["loss_weights"] = trainer.dynamic_loss.trainable_weight.detach().cpu()
     torch.save(state, path)
 
 
@@ -549,7 +808,7 @@ def _resume_training(trainer, state):
     assert len(state["schedulers"]) == 1, "Wrong lengths of schedulers"
     trainer.optimizer.load_state_dict(state["optimizers"][0])
     trainer.step_count = int(state["schedulers"][0]["last_epoch"])
-    if "loss_weights" in state:
+    if "loss_weights" in state and trainer.dynamic_loss is not None:
         with torch.no_grad():
             trainer.dynamic_loss.trainable_weight.copy_(state["loss_weights"].to(trainer.dynamic_loss.trainable_weight.device))
     return state.get("epoch", 0), state.get("iter", trainer.step_count)

@@ -34,6 +34,26 @@ def ssim_weight(opt):
     return float(o['ssim_weight']) if o.get('use_ssim_criterion') else None
 
 
+def criteria(opt):
+    """The criterion arguments of ``harness.Trainer`` from an option tree's ``train:`` block (F_model_depthCond.py:50-59,
+    78-84): ``pixel_criterion`` / ``pixel_weight``, ``dynamic_loss.{use_dynamic_criterion, dynamic_criterion,
+    dynamic_weight}`` and ``mask_loss.{use_mask_criterion, mask_criterion, mask_weight}``.  A ``use_*: false`` key maps to
+    None (``dynamic_weight=None`` / ``mask_criterion=None``: the term is off); a missing key or block maps to the Trainer's
+    default, so ``Trainer(net, **criteria({}))`` is ``Trainer(net)``."""
+    t = opt.get('train') or {}
+    out = dict(pixel_criterion=t.get('pixel_criterion', 'l1'), pixel_weight=float(t.get('pixel_weight', 1.0)),
+               dynamic_criterion='smoothl1', dynamic_weight=10.0, mask_criterion=None, mask_weight=1.0)
+    d = t.get('dynamic_loss')
+    if d is not None:
+        out['dynamic_criterion'] = d.get('dynamic_criterion', 'smoothl1')
+        out['dynamic_weight'] = float(d.get('dynamic_weight', 10.0)) if d.get('use_dynamic_criterion', True) else None
+    m = t.get('mask_loss') or {}
+    if m.get('use_mask_criterion'):
+        out['mask_criterion'] = m.get('mask_criterion', 'smoothl1')
+        out['mask_weight'] = float(m.get('mask_weight', 1.0))
+    return out
+
+
 X8_NETWORK_G = dict(which_model_G='DepthNet', which_ResBlk_depth=list(range(14)), in_nc=3, out_nc=3, nf=64, nb=16,
                     upscale=8, code_length=10, depth_latent_ch=256, norm_type='weight_norm',
                     use_trainable_params=True, norm_gamma=0.1, norm_beta=0.1, ablate_depth_block=False,

@@ -860,6 +860,54 @@ def loss_bwd_soft(sr, hr, mask, dsums, K):
     return dsr
 
 
+# ---- harness losses with the criteria as arguments (region bytes or soft masks) ------------------
+CRIT_CODES = {"l1": 0, "l2": 1, "cb": 2, "smoothl1": 3}       # DASR_CRIT_*; None -> DASR_CRIT_NONE
+
+
+def _crit_args(pixel, crit_a, crit_b):
+    return CRIT_CODES[pixel], CRIT_CODES[crit_a], -1 if crit_b is None else CRIT_CODES[crit_b]
+
+
+def _crit_dims(sr, aux, K):
+    """``aux``: region bytes [B,h,w] (uint8, dasr_mask_compress) or float masks [B,K,h,w]; -> (soft, B, C, h, w, scale)."""
+    if aux.dtype == torch.uint8:
+        B, C, H, W = sr.shape
+        _, h, w = aux.shape
+        scale = H // h
+        assert aux.shape[0] == B and H == h * scale and W == w * scale
+        return False, B, C, h, w, scale
+    return (True,) + _soft_loss_dims(sr, aux, K)
+
+
+def loss_sums_crit(sr, hr, aux, K, pixel, crit_a, crit_b=None):
+    """K numerators of criterion A | K areas | the pixel criterion's sum | with ``crit_b``: K numerators of criterion B
+    (dasr_loss_sums_crit / dasr_loss_sums_soft_crit).  ``pixel``: 'l1' | 'l2' | 'cb'; ``crit_a`` / ``crit_b``:
+    'l1' | 'l2' | 'smoothl1'."""
+    soft, B, C, h, w, scale = _crit_dims(sr, aux, K)
+    assert hr.shape == sr.shape
+    sums = empty(((2 if crit_b is None else 3) * K + 1,), sr)
+    if soft:
+        _call("dasr_loss_sums_soft_crit", _p(sr), _p(hr), _p(aux), _p(sums), B, C, h, w, scale, K, *_crit_args(pixel, crit_a, crit_b))
+    else:
+        _call("dasr_loss_sums_crit", _p(sr), _p(hr), _lib.ptr(aux, dtype=torch.uint8), _p(sums), B, C, h, w, scale, K,
+              *_crit_args(pixel, crit_a, crit_b))
+    return sums
+
+
+def loss_bwd_crit(sr, hr, aux, dsums, K, pixel, crit_a, crit_b=None):
+    """dsr from the device vector ``dsums`` (the layout of loss_sums_crit's result; the areas' entries are not read)."""
+    soft, B, C, h, w, scale = _crit_dims(sr, aux, K)
+    assert hr.shape == sr.shape and dsums.numel() == (2 if crit_b is None else 3) * K + 1
+    dsr = torch.empty_like(sr)
+    if soft:
+        _call("dasr_loss_bwd_soft_crit", _p(sr), _p(hr), _p(aux), _p(dsums), _p(dsr), B, C, h, w, scale, K,
+              *_crit_args(pixel, crit_a, crit_b))
+    else:
+        _call("dasr_loss_bwd_crit", _p(sr), _p(hr), _lib.ptr(aux, dtype=torch.uint8), _p(dsums), _p(dsr), B, C, h, w, scale, K,
+              *_crit_args(pixel, crit_a, crit_b))
+    return dsr
+
+
 # ---- SSIM: validation metric and training criterion (csrc/ssim.hip, csrc/ssim_bwd.hip) ----------
 _ssim_window = None
 

@@ -379,6 +379,34 @@ int dasr_loss_sums_soft(const float* sr, const float* hr, const float* mask, flo
                         int scale, int K, void* stream);
 int dasr_loss_bwd_soft(const float* sr, const float* hr, const float* mask, const float* dsums, float* dsr, int B, int C,
                        int h, int w, int scale, int K, void* stream);
+/* The same two passes with the criteria as ARGUMENTS - what a reference yml can switch on beside the defaults:
+ * pixel_crit: train.pixel_criterion l1 | l2 | cb (nn.L1Loss / nn.MSELoss / CharbonnierLoss, F_model_depthCond.py:50-58,164;
+ * loss.py:37-47); crit_a: dynamic_loss.dynamic_criterion l1 | l2 | smoothl1 (mask_loss.py:44-90); crit_b: a second region
+ * criterion for mask_loss (mask_loss.py:6-41, F_model_depthCond.py:183-186) when mask_criterion differs from
+ * dynamic_criterion, else DASR_CRIT_NONE.  They replace nn.L1Loss / nn.MSELoss / CharbonnierLoss on (sr, hr) and the K
+ * (2K) masked passes of those two modules.  With d = sr - hr and M_k the nearest-upsampled mask:
+ * sums = K numerators of A | K areas (as above) | pixel sum | with crit_b: K numerators of B   ([2K+1], [3K+1] with crit_b)
+ *   pixel sum: sum |d| (l1), sum d^2 (l2), sum sqrt(d^2 + 1e-6) (cb)
+ *   numerator k: sum |M_k d| (l1), sum (M_k d)^2 (l2), sum smooth_l1(M_k d), beta 1 (smoothl1); the mask is INSIDE
+ * (region bytes: the criterion of d over the region's pixels).  Means / ratios / weights stay in PyTorch.
+ * bwd: dsr = dsums[2K] * pix'(d) + sum_k M_k (dsums[k] A'(M_k d) + dsums[2K+1+k] B'(M_k d)), with l1' = sign (sign(0) = 0),
+ * l2' = 2u, cb' = d / sqrt(d^2 + 1e-6), smooth_l1' = u for |u| < 1 else sign(u).  dsums: DEVICE vector of the sums' length
+ * (the areas' entries are not read); nothing is read back to the host, so both passes can be captured.
+ * cb as a region criterion, smoothl1 as the pixel criterion, any other code and K > 16: DASR_E_UNSUPPORTED before a launch.
+ * (pixel l1, A smoothl1, no B) computes what the four entry points above compute; they remain what the defaults run. */
+#define DASR_CRIT_NONE (-1)
+#define DASR_CRIT_L1 0
+#define DASR_CRIT_L2 1
+#define DASR_CRIT_CB 2
+#define DASR_CRIT_SMOOTHL1 3
+int dasr_loss_sums_crit(const float* sr, const float* hr, const unsigned char* region, float* sums, int B, int C, int h,
+                        int w, int scale, int K, int pixel_crit, int crit_a, int crit_b, void* stream);
+int dasr_loss_bwd_crit(const float* sr, const float* hr, const unsigned char* region, const float* dsums, float* dsr,
+                       int B, int C, int h, int w, int scale, int K, int pixel_crit, int crit_a, int crit_b, void* stream);
+int dasr_loss_sums_soft_crit(const float* sr, const float* hr, const float* mask, float* sums, int B, int C, int h, int w,
+                             int scale, int K, int pixel_crit, int crit_a, int crit_b, void* stream);
+int dasr_loss_bwd_soft_crit(const float* sr, const float* hr, const float* mask, const float* dsums, float* dsr, int B,
+                            int C, int h, int w, int scale, int K, int pixel_crit, int crit_a, int crit_b, void* stream);
 
 /* ---- small elementwise helpers ---------------------------------------------------------------- */
 int dasr_add(const float* a, const float* b, float* out, size_t n, void* stream);  /* torch.add, sftmd_arch.py:931 */
