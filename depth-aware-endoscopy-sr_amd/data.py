@@ -86,7 +86,7 @@ def draw_augment(rng, B, use_flip=True, use_rot=True):
 class _Buffers:
     """Static buffers of one input shape: the uploads, the per-sample tables, the resize tables and the four outputs."""
 
-    def __init__(self, B, H, W, s, ch, cw, K, crop, device):
+    def __init__(self, B, H, W, s, ch, cw, K, crop, device, soft=False):
         h, w = H // s, W // s
         dev = device
         self.frames = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
@@ -100,10 +100,12 @@ class _Buffers:
         self.gt = torch.empty((B, 3, s * ch, s * cw), dtype=torch.float32, device=dev)
         self.depth = torch.empty((B, 1, ch, cw), dtype=torch.float32, device=dev)
         self.masks = torch.empty((B, K, ch, cw), dtype=torch.float32, device=dev)
-        self.region = torch.empty((B, ch, cw), dtype=torch.uint8, device=dev)
+        if not soft:                                 # soft masks have no region bytes
+            self.region = torch.empty((B, ch, cw), dtype=torch.uint8, device=dev)
         if crop:                                     # the masks of the full depth map, before the window is cut out
             self.full_masks = torch.empty((B, K, h, w), dtype=torch.float32, device=dev)
-            self.full_region = torch.empty((B, h, w), dtype=torch.uint8, device=dev)
+            if not soft:
+                self.full_region = torch.empty((B, h, w), dtype=torch.uint8, device=dev)
         if dev.type == "cuda":
             self.pin_frames = torch.empty((B, H, W, 3), dtype=torch.uint8).pin_memory()
             self.pin_depth = torch.empty((B, 1, h, w), dtype=torch.float32).pin_memory()
@@ -127,6 +129,14 @@ class BatchMaker:
     FULL depth map first (a window has another minimum and maximum), then the K planes and the region bytes are cut and
     augmented like the depth map (``ops.batch_plane``, float32 and uint8).
 
+    ``soft_masks=None``: the reference's one-hot masks, as above.  A number in (0, 1] is the blend ``width`` of
+    ``prep.depth_to_soft_masks``: ``masks`` are hat-function planes (``dasr_depth_to_masks_soft``), binned from the
+    augmented depth map without crop (the rule is pointwise given a sample's minimum and maximum, so this equals
+    augmenting the planes) and from the FULL depth map, then cut and augmented as float32 planes, with crop.  No region
+    bytes exist in this mode (none are allocated); ``masks`` is re-stamped soft (``prep.mark_soft``'s stamp) after every
+    ``make``.  ``harness.Trainer`` needs nothing else: it already takes soft-stamped masks through the soft-mask kernels,
+    eagerly and captured (``use_graph=True``), without a read-back.
+
     **Lifetime.**  The four results are this object's static buffers of the input shape: the next ``make`` with frames of
     the same shape overwrites them, in stream order.  Consume them (on the same stream) before calling ``make`` again,
     or ``clone()`` them.  That is what lets ``Trainer(use_graph=True)`` see the same addresses every step and skip its
@@ -135,12 +145,18 @@ class BatchMaker:
     GPU are copied into the static frame buffer too (device to device; 63 MB at 16 frames of 1024x1280): the chain, and a
     graph captured over it, always reads the same addresses."""
 
-    def __init__(self, scale, num_masks=10, fixed_range=False, crop=None, device=None, max_shapes=4):
+    def __init__(self, scale, num_masks=10, fixed_range=False, crop=None, device=None, max_shapes=4, soft_masks=None):
         self.scale = int(scale)
         if self.scale not in SCALES:
             raise ValueError("BatchMaker: scale must be one of %s, got %r" % (SCALES, scale))
         self.num_masks = int(num_masks)
         self.fixed_range = bool(fixed_range)
+        self.soft_masks = None if soft_masks is None else float(soft_masks)
+        if self.soft_masks is not None:
+            if not 0.0 < self.soft_masks <= 1.0:
+                raise ValueError("BatchMaker: soft_masks is the blend width, in (0, 1], got %r" % (soft_masks,))
+            if not 1 <= self.num_masks <= 16:
+                raise ValueError("BatchMaker: soft masks take 1..16 regions, got %d" % self.num_masks)
         self.crop = None if crop is None else (int(crop[0]), int(crop[1]))
         if self.crop is not None and min(self.crop) <= 0:
             raise ValueError("BatchMaker: crop must be positive, got %r" % (crop,))
@@ -165,7 +181,8 @@ class BatchMaker:
                 if self.device.type == "cuda":
                     torch.cuda.synchronize(self.device)
                 self._shapes.pop(next(iter(self._shapes)))
-            buf = _Buffers(B, H, W, s, ch, cw, self.num_masks, self.crop is not None, self.device)
+            buf = _Buffers(B, H, W, s, ch, cw, self.num_masks, self.crop is not None, self.device,
+                           soft=self.soft_masks is not None)
         self._shapes[key] = buf                   # most recently used last
         return buf, ch, cw
 
@@ -237,6 +254,14 @@ class BatchMaker:
         ops.batch_lr_u8(buf.frames, s, buf.tables, win, origins, buf.flags, transpose, out=buf.lq)
         ops.batch_gt_u8(buf.frames, s, win, origins, buf.flags, transpose, out=buf.gt)
         ops.batch_plane(buf.depth_in, win, origins, buf.flags, transpose, out=buf.depth)
+        if self.soft_masks is not None:
+            if self.crop is None:
+                ops.depth_to_masks_soft(buf.depth, K, self.soft_masks, self.fixed_range, out=buf.masks)
+            else:
+                ops.depth_to_masks_soft(buf.depth_in, K, self.soft_masks, self.fixed_range, out=buf.full_masks)
+                ops.batch_plane(buf.full_masks, win, origins, buf.flags, transpose, out=buf.masks)
+            prep.mark_soft(buf.masks)                # soft: the general kernels, no read-back of a one-hot flag
+            return
         if self.crop is None:
             ops.depth_to_masks(buf.depth, K, self._edges, out=(buf.masks, buf.region))
         else:

@@ -744,6 +744,33 @@ def depth_to_masks(depth, num_masks=10, fixed_edges=None, want_planes=True, out=
     return planes, region
 
 
+def depth_to_masks_soft(depth, num_masks=10, width=1.0, fixed_range=False, out=None):
+    """Soft (hat-function) membership planes (dasr_depth_to_masks_soft): depth [B,1,h,w] or [B,h,w] float32 -> planes
+    [B,K,h,w] float32, at most two non-zero per pixel, summing to 1.  ``width`` in (0, 1]: the share of a bin over which
+    two neighbours blend (1: linear interpolation between bin centres).  ``fixed_range``: bins over [0,1] instead of the
+    sample's own [min, max].  ``out``: a ``[B,K,h,w]`` buffer to write into instead of a new one."""
+    if depth.dtype != torch.float32:
+        raise TypeError("depth_to_masks_soft: depth must be float32, got %s" % depth.dtype)
+    if not 0.0 < float(width) <= 1.0:                    # False for NaN too
+        raise ValueError("depth_to_masks_soft: width must be in (0, 1], got %r" % (width,))
+    if not 1 <= int(num_masks) <= 16:
+        raise ValueError("depth_to_masks_soft: num_masks must be in 1..16, got %r" % (num_masks,))
+    h, w = depth.shape[-2:]
+    B = depth.numel() // (h * w)
+    d = depth.contiguous()
+    if out is not None:
+        planes = out
+        if tuple(planes.shape) != (B, num_masks, h, w):
+            raise ValueError("depth_to_masks_soft: out must be [%d,%d,%d,%d], got %s" % (B, num_masks, h, w, tuple(planes.shape)))
+    else:
+        planes = torch.empty((B, num_masks, h, w), dtype=torch.float32, device=d.device)
+    nbytes = int(_lib.get().dasr_depth_to_masks_soft_workspace(B, h * w))
+    ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=d.device)
+    _call("dasr_depth_to_masks_soft", _p(d), _p(planes), _p(ws), nbytes, B, h * w, int(num_masks), float(width),
+          int(bool(fixed_range)))
+    return planes
+
+
 def _rf(region, flag):
     if region is None:
         return None, None

@@ -65,6 +65,23 @@ def mark_soft(masks):
     return masks
 
 
+def depth_to_soft_masks(depth, num_masks=10, fixed_range=False, width=1.0):
+    """``depth`` ``[B,1,h,w]`` (or ``[B,h,w]``) float32 -> soft ``DepthMaskList`` ``[B,K,h,w]`` float32: hat-function
+    membership in the K depth bins of ``depth_to_masks`` (``dasr_depth_to_masks_soft``; the rule is in include/dasr.h).
+    ``width`` in (0, 1] is the share of a bin over which two neighbouring regions blend: 1 interpolates linearly between
+    bin centres, a small width approaches the one-hot binning - but stays continuous in the depth value and in the
+    sample's range, which the one-hot planes are not (a pixel crossing an edge switches region).  At most two planes are
+    non-zero per pixel and they sum to 1; the maximum pixel belongs to plane K-1 (the one-hot rule leaves it in no bin).
+
+    The result is stamped like ``mark_soft`` output: ``attach_region`` answers False at once, so ``harness.fused_losses``
+    and a ``Trainer`` step (eager or captured) take the general (soft-mask) kernels without a compression pass of their
+    own and without reading a flag back."""
+    # (the op raises TypeError for a depth that is not float32, ValueError for a width outside (0, 1] or more than 16 masks)
+    planes = ops.depth_to_masks_soft(depth, int(num_masks), float(width), bool(fixed_range))
+    _stamp(planes, None, True)
+    return planes
+
+
 def attach_region(masks):
     """Give a mask tensor that did NOT come from ``depth_to_masks`` (e.g. the reference's CPU dataloader output moved to
     the GPU) its region bytes, so that the generator and the fused loss take the one-hot kernels without ever reading

@@ -83,7 +83,7 @@ def validate(net, frames, scale):
     return psnr_sum / max(n, 1), ssim_sum / max(n, 1), n
 
 
-def validate_u8(net, frames, scale, num_masks=10, fixed_range=False, use_graph=False):
+def validate_u8(net, frames, scale, num_masks=10, fixed_range=False, use_graph=False, soft_masks=None):
     """The loop of ``validate()`` for a video source: ``frames`` yields ``(LQ, GT, Depth)`` with ``LQ`` a ``uint8``
     ``[1,h,w,3]`` (or ``[h,w,3]``) BGR frame as ``cv2`` reads it, ``GT`` the ``[1,3,sh,sw]`` float tensor and ``Depth``
     ``[1,1,h,w]``; a fourth item (the reference loader's mask list) is ignored, the masks are binned on the device.
@@ -91,10 +91,12 @@ def validate_u8(net, frames, scale, num_masks=10, fixed_range=False, use_graph=F
     ``20 log10(255 / sqrt(ssd / n))`` from the exact integer sum of squared differences of the two uint8 images with a
     ``scale``-pixel border cropped (``dasr_frame_ssd_u8``; ``inf`` at ``ssd == 0``); SSIM is ``dasr_ssim`` of the [0,1]
     tensors as in ``validate()``.  Nothing is read back per frame: the sums stay on the device and come to the host in
-    one transfer at the end.  Returns (avg_psnr, avg_ssim, n)."""
+    one transfer at the end.  ``soft_masks``: ``FrameUpscaler``'s (None: one-hot masks; a number: soft masks of that blend
+    width).  Returns (avg_psnr, avg_ssim, n)."""
     from . import ops
     from .video import FrameUpscaler
-    up = FrameUpscaler(net, num_masks=num_masks, fixed_range=fixed_range, use_graph=use_graph, min_max=(0, 1))
+    up = FrameUpscaler(net, num_masks=num_masks, fixed_range=fixed_range, use_graph=use_graph, min_max=(0, 1),
+                       soft_masks=soft_masks)
     dev = up.device
     CHUNK = 256
     chunks, counts = [], []              # int64 [2*CHUNK] each: ssd in the first half, ssim (float32 bits) in the second

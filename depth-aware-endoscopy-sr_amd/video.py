@@ -63,6 +63,12 @@ class FrameUpscaler:
     ``net.set_compute_dtype``); ``net.min`` / ``net.max`` are the clamp of the network's output, ``min_max`` is
     ``tensor2img``'s range.
 
+    ``soft_masks=None``: the reference's one-hot depth masks.  A number in (0, 1] is the blend ``width`` of
+    ``prep.depth_to_soft_masks``: the chain bins the depth map into hat-function planes (``dasr_depth_to_masks_soft``) and
+    the network runs its soft-mask kernels, so the output is continuous in the depth map from frame to frame; the result
+    is then what ``validate.test`` gives with ``prep.depth_to_soft_masks(depth, num_masks, fixed_range, width)``.  It is a
+    constructor constant (not part of a captured graph's signature).
+
     ``use_graph=True`` (GPU only, ignored elsewhere): the first two calls of an input shape run eagerly - the fold cache,
     the allocator's pools and the side stream of the depth branch come into being - the third captures
     ingest -> masks -> forward -> emit into one graph over static buffers and replays it, later calls copy in, replay and
@@ -71,10 +77,13 @@ class FrameUpscaler:
     compares per kernel), and on a mismatch the graph is dropped and the shape starts its warm-up again.  One graph per
     input shape (two when ``upscale_iter`` is used), for the ``max_shapes`` most recently used shapes."""
 
-    def __init__(self, net, num_masks=10, fixed_range=False, use_graph=True, min_max=(0, 1), max_shapes=4):
+    def __init__(self, net, num_masks=10, fixed_range=False, use_graph=True, min_max=(0, 1), max_shapes=4, soft_masks=None):
         self.net = net
         self.num_masks = int(num_masks)
         self.fixed_range = bool(fixed_range)
+        self.soft_masks = None if soft_masks is None else float(soft_masks)
+        if self.soft_masks is not None and not 0.0 < self.soft_masks <= 1.0:
+            raise ValueError("FrameUpscaler: soft_masks is the blend width, in (0, 1], got %r" % (soft_masks,))
         self.min_max = (min_max[0], min_max[1])
         p = next(net.parameters())
         self.device = p.device
@@ -110,9 +119,13 @@ class FrameUpscaler:
     # ---- the chain -----------------------------------------------------------------------------------------------------
     def _chain(self, slot):
         ops.frame_ingest_u8(slot.frames, swap_rb=True, out=slot.x)
-        planes, region = ops.depth_to_masks(slot.depth, self.num_masks, self._edges, want_planes=True)
-        planes._dasr_region = region                     # as prep.depth_to_masks: no compression pass, no flag read-back
-        planes._dasr_version = ops.tensor_version(planes)
+        if self.soft_masks is not None:
+            planes = ops.depth_to_masks_soft(slot.depth, self.num_masks, self.soft_masks, self.fixed_range)
+            prep.mark_soft(planes)                       # as prep.depth_to_soft_masks: the general kernels, no read-back
+        else:
+            planes, region = ops.depth_to_masks(slot.depth, self.num_masks, self._edges, want_planes=True)
+            planes._dasr_region = region                 # as prep.depth_to_masks: no compression pass, no flag read-back
+            planes._dasr_version = ops.tensor_version(planes)
         slot.y = self.net.infer_nhwc(slot.x, slot.depth, planes)
         ops.frame_emit_u8(slot.y, self.net.min, self.net.max, self.min_max, swap_rb=True, out=slot.out)
 

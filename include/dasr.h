@@ -358,6 +358,25 @@ size_t dasr_depth_to_masks_workspace(int B, int HW);
 int dasr_depth_to_masks(const float* depth, const float* fixed_edges, float* masks, unsigned char* region,
                         void* workspace, size_t workspace_bytes, int B, int HW, int K, void* stream);
 
+/* dasr_depth_to_masks_soft: soft (hat-function) membership in the same K bins, for the soft-mask kernels.  Per sample
+ * lo, hi = min, max of the map (fixed_range != 0: lo = 0, hi = 1 and no min / max pass), interval = (hi - lo) / K, and
+ * per pixel, in float32 with every operation rounded on its own (no FMA contraction, IEEE division):
+ *   interval not > 0 (constant map): plane 0 = 1, all others 0 (the one-hot rule leaves such a map in no bin)
+ *   u = min(max((v - lo) / interval, 0), K)         fixed range: values outside [0,1] go to the end planes
+ *   k = min((int)floorf(u), K - 1);  r = u - k      r in [0,1]; r == 1 only at u == K, the maximum
+ *   r < 0.5:  n = k - 1, s = 0.5 - r / width        else:  n = k + 1, s = 0.5 - (1 - r) / width
+ *   s = max(s, 0), and s = 0 where n < 0 or n >= K;  plane[k] = 1 - s, plane[n] = s, every other plane 0
+ * width = 1: linear interpolation between bin centres; a smaller width narrows the blend to a band of width * interval
+ * around each interior edge (0.5 / 0.5 on the edge, from both sides); width -> 0 tends to the binning above.  At most two
+ * planes are non-zero per pixel and they sum to 1; every plane is Lipschitz in v with constant 1 / (interval * width).
+ * The MAXIMUM pixel belongs to plane K-1 here; the one-hot rule above (the reference's) leaves it in no bin.
+ * NaN depth: unspecified.  masks: NCHW [B,K,HW] float32, every element written (no memset needed); any alignment (16-byte
+ * stores where the address allows, scalar stores elsewhere).  0 < width <= 1, else (NaN included) DASR_E_SHAPE;
+ * K > 16: DASR_E_UNSUPPORTED.  workspace: dasr_depth_to_masks_soft_workspace() bytes (required in both modes). */
+size_t dasr_depth_to_masks_soft_workspace(int B, int HW);
+int dasr_depth_to_masks_soft(const float* depth, float* masks, void* workspace, size_t workspace_bytes, int B, int HW,
+                             int K, float width, int fixed_range, void* stream);
+
 /* ---- harness losses in one pass (one-hot and soft masks) ----------------------------------
  * nn.L1Loss + dynamic_weight_mask_loss('smoothl1') (F_model_depthCond.py:164,188-190; mask_loss.py:64-90) need, per
  * depth region k, sum smooth_l1(m_k*sr, m_k*hr) and sum m_k (masks nearest-upsampled to HR), and sum |sr-hr|.

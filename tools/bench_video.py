@@ -6,7 +6,9 @@
   c  video.FrameUpscaler(use_graph=True).upscale          (captured graph, replayed)
   d  video.FrameUpscaler(use_graph=True).upscale_iter     (two-slot pipeline; per frame = time between two results)
 
-for one configuration (--config x8: the x8 net on a 128x160 frame; x2: the x2 net on a 540x960 frame; --dtype fp32|bf16).
+for one configuration (--config x8: the x8 net on a 128x160 frame; x2: the x2 net on a 540x960 frame; --dtype fp32|bf16;
+--soft-masks WIDTH: soft depth masks of that blend width in every arm, default one-hot; its entry's key ends in _softWIDTH).
+tools/bench_soft_prep.py compares the two mask kinds in one process, alternating.
 Every arm gets --warmup frames, then --rounds rounds of --frames frames; the arms alternate within a round.  Each timed
 call ends in a device synchronise (a: the download; b, c: the stream synchronise of upscale; d: the download event of the
 frame handed out).  Median and p95 over all timed frames of an arm, and the median of each round, go into one entry of
@@ -40,6 +42,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--arms", default="abcd")
+    ap.add_argument("--soft-masks", type=float, default=None, metavar="WIDTH",
+                    help="soft depth masks of this blend width (prep.depth_to_soft_masks) in every arm; default: one-hot")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     sys.path.insert(0, a.root)
@@ -66,12 +70,14 @@ def main():
         img = f[0].astype(np.float32) / 255.                                   # img2tensor, utils/util.py:596-605
         lq = torch.from_numpy(np.ascontiguousarray(np.transpose(img[:, :, [2, 1, 0]], (2, 0, 1))))[None].to(dev)
         dd = torch.from_numpy(d).to(dev)
-        sr = validate.test(net, lq, dd, prep.depth_to_masks(dd, K))
+        mk = prep.depth_to_masks(dd, K) if soft is None else prep.depth_to_soft_masks(dd, K, width=soft)
+        sr = validate.test(net, lq, dd, mk)
         return validate.tensor2img(sr[0])[None]                                # download + clamp / transpose / round on the host
 
-    up_b = FrameUpscaler(net, num_masks=K, use_graph=False)
-    up_c = FrameUpscaler(net, num_masks=K, use_graph=True)
-    up_d = FrameUpscaler(net, num_masks=K, use_graph=True)
+    soft = a.soft_masks
+    up_b = FrameUpscaler(net, num_masks=K, use_graph=False, soft_masks=soft)
+    up_c = FrameUpscaler(net, num_masks=K, use_graph=True, soft_masks=soft)
+    up_d = FrameUpscaler(net, num_masks=K, use_graph=True, soft_masks=soft)
 
     def per_call(fn):
         def run(n):
@@ -108,7 +114,7 @@ def main():
             torch.cuda.synchronize()
             allms[k] += ms
             rounds[k].append(stats(ms)["median_ms"])
-    entry = dict(config=a.config, dtype=a.dtype, scale=scale, lr_hw=[h, w], frames=a.frames, rounds=a.rounds,
+    entry = dict(config=a.config, dtype=a.dtype, soft_masks=soft, scale=scale, lr_hw=[h, w], frames=a.frames, rounds=a.rounds,
                  warmup=a.warmup, outputs_equal_to_b=same, graph_replays=dict(c=up_c.replays, d=up_d.replays),
                  arms={k: dict(stats(v), round_medians_ms=rounds[k]) for k, v in allms.items()},
                  device=torch.cuda.get_device_name(0), peak_mem_gb=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2))
@@ -118,7 +124,7 @@ def main():
         if os.path.exists(a.out):
             with open(a.out) as fh:
                 data = json.load(fh)
-        data["%s_%s" % (a.config, a.dtype)] = entry
+        data["%s_%s%s" % (a.config, a.dtype, "" if soft is None else "_soft%g" % soft)] = entry
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as fh:
             json.dump(data, fh, indent=1, sort_keys=True)
