@@ -6,13 +6,16 @@ L1 pixel loss (weight 1) + dynamic depth-aware smooth-L1 loss (weight 10, 10 tra
 weights, codes/models/modules/mask_loss.py:44-90), Adam(lr 1e-3, betas (0.9, 0.99), wd 0) over the
 generator's parameters plus the loss weights, CosineAnnealingLR_Restart stepped BEFORE the optimiser
 (codes/models/lr_scheduler.py:34-62).  Losses and optimiser stay PyTorch (north_star); the generator
-forward/backward is the HIP path, and so are the sums both losses need (``fused_losses``: one pass over sr / hr for one-hot
-masks and for soft masks alike; the division, the softmax weighting and the collective stay in PyTorch).  The reference's
-optional SSIM criterion (``Trainer(ssim_weight=...)``, off by default as in the shipped ymls) is ``SSIMLoss``: ``dasr_ssim``
-forward, ``dasr_ssim_bwd`` backward, in the fused losses' autograd node and collective when both are on.  The other criteria
-a reference yml can name - ``pixel_criterion`` l1 / l2 / cb, ``dynamic_criterion`` l1 / l2 / smoothl1, the dynamic term off,
-the static ``mask_loss`` - are ``Trainer`` arguments too (``networks.criteria(opt)``); any combination but the default goes
-through ``criterion_losses``: one ``dasr_loss_sums[_soft]_crit`` pass forward, one ``dasr_loss_bwd[_soft]_crit`` backward.
+forward/backward is the HIP path, and so are the sums every loss term needs: ONE autograd node (``_LossSums``: one pass over
+sr / hr forward, one backward, for one-hot masks and for soft masks alike), ONE rule for when the kernels take the tensors
+(``_criterion_aux``) and ONE piece of arithmetic after the sums (``_compose_losses``: the division, the softmax weighting and
+the collective stay in PyTorch).  The criteria a reference yml can name - ``pixel_criterion`` l1 / l2 / cb,
+``dynamic_criterion`` l1 / l2 / smoothl1, the dynamic term off, the static ``mask_loss`` - are ``Trainer`` arguments
+(``networks.criteria(opt)``).  The default combination (pixel l1, dynamic smooth-L1, no static mask) runs the kernels that
+have it compiled in (``dasr_loss_{sums,bwd}[_soft]``, through ``fused_losses``), any other the same kernels with the criteria
+as arguments (``dasr_loss_{sums,bwd}[_soft]_crit``, through ``criterion_losses``).  The reference's optional SSIM criterion
+(``Trainer(ssim_weight=...)``, off by default as in the shipped ymls) is ``SSIMLoss``: ``dasr_ssim`` forward, ``dasr_ssim_bwd``
+backward, in the same autograd node and collective when its kernels take the tensors.
 
 Data parallel: one process per GPU (torchrun), ``torch.distributed`` backend ``nccl`` (= RCCL over
 xGMI) on the GPU box, ``gloo`` in CPU tests.  The net itself is communication-free (instance norm is
@@ -46,45 +49,6 @@ def _world(group=None):
     if torch.distributed.is_available() and torch.distributed.is_initialized():
         return torch.distributed.get_world_size(group)
     return 1
-
-
-class _RegionSums(torch.autograd.Function):
-    """sums = (K smooth-L1 numerators | K areas | sum|sr-hr|) in ONE pass over sr, hr (dasr_loss_sums); the
-    backward is one elementwise pass (dasr_loss_bwd).  One-hot masks (region bytes from dasr_mask_compress)."""
-
-    @staticmethod
-    def forward(ctx, sr, hr, region, K):
-        from . import ops
-        sr_c, hr_c = sr.contiguous(), hr.contiguous()
-        ctx.save_for_backward(sr_c, hr_c, region)
-        ctx.K = K
-        return ops.loss_sums(sr_c, hr_c, region, K)
-
-    @staticmethod
-    def backward(ctx, dsums):
-        from . import ops
-        sr, hr, region = ctx.saved_tensors
-        return ops.loss_bwd(sr, hr, region, dsums.contiguous(), ctx.K), None, None, None
-
-
-class _RegionSumsSoft(torch.autograd.Function):
-    """The same sums for arbitrary float masks [B,K,h,w] (dasr_loss_sums_soft / dasr_loss_bwd_soft): the mask sits inside
-    the smooth-L1, so every pixel feeds all K numerators - still one pass forward and one backward.  K <= 16; no gradient
-    to the masks."""
-
-    @staticmethod
-    def forward(ctx, sr, hr, mask, K):
-        from . import ops
-        sr_c, hr_c, mask_c = sr.contiguous(), hr.contiguous(), mask.detach().contiguous()
-        ctx.save_for_backward(sr_c, hr_c, mask_c)
-        ctx.K = K
-        return ops.loss_sums_soft(sr_c, hr_c, mask_c, K)
-
-    @staticmethod
-    def backward(ctx, dsums):
-        from . import ops
-        sr, hr, mask = ctx.saved_tensors
-        return ops.loss_bwd_soft(sr, hr, mask, dsums.contiguous(), ctx.K), None, None, None
 
 
 def ssim_torch(img1, img2):
@@ -127,28 +91,50 @@ class _SSIM(torch.autograd.Function):
         return ops.ssim_bwd(img1, img2, _dscale(dS)), None
 
 
-class _RegionSumsSSIM(torch.autograd.Function):
-    """(_RegionSums or _RegionSumsSoft, _SSIM) as ONE node: the 9x9 dgrad takes dL/dsr as one tensor, so the SSIM backward
-    adds into the dsr the loss backward has just written (dasr_ssim_bwd, accumulate) instead of autograd adding two
-    HR-sized tensors in a pass of its own.  ``aux``: region bytes (``soft`` False) or float masks (``soft`` True)."""
+class _LossSums(torch.autograd.Function):
+    """sums = (K numerators of criterion A | K areas | pixel-criterion sum [| K numerators of criterion B]) in ONE pass over
+    sr, hr, and one elementwise backward.  ``aux``: region bytes (uint8, from dasr_mask_compress) or float masks [B,K,h,w] -
+    the mask then sits inside the criterion, so every pixel feeds all K numerators; K <= 16; no gradient to the masks.
+    ``crits``: None - the default criteria (pixel l1, region smooth-L1, no B) through the kernels that have them compiled in
+    (ops.loss_sums / loss_bwd, ops.loss_sums_soft / loss_bwd_soft); a tuple (pixel, A, B or None) - the criteria as kernel
+    arguments (ops.loss_sums_crit / loss_bwd_crit), the default ones included.
+    ``with_ssim``: a second output, the SSIM criterion of (sr, hr) - the 9x9 dgrad takes dL/dsr as one tensor, so the SSIM
+    backward adds into the dsr the loss backward has just written (dasr_ssim_bwd, accumulate) instead of autograd adding two
+    HR-sized tensors in a pass of its own."""
 
     @staticmethod
-    def forward(ctx, sr, hr, aux, K, soft):
+    def _ops(aux, crits):
+        """(sums op, backward op, trailing arguments), looked up on ``ops`` at call time."""
+        from . import ops
+        if crits is not None:
+            return ops.loss_sums_crit, ops.loss_bwd_crit, crits
+        if aux.dtype == torch.uint8:
+            return ops.loss_sums, ops.loss_bwd, ()
+        return ops.loss_sums_soft, ops.loss_bwd_soft, ()
+
+    @staticmethod
+    def forward(ctx, sr, hr, aux, K, crits, with_ssim):
         from . import ops
         sr_c, hr_c = sr.contiguous(), hr.contiguous()
-        aux = aux.detach().contiguous() if soft else aux
+        if aux.dtype != torch.uint8:
+            aux = aux.detach().contiguous()
         ctx.save_for_backward(sr_c, hr_c, aux)
-        ctx.K, ctx.soft = K, soft
-        sums = (ops.loss_sums_soft if soft else ops.loss_sums)(sr_c, hr_c, aux, K)
-        return sums, ops.ssim(sr_c, hr_c).mean()
+        ctx.K, ctx.crits, ctx.with_ssim = K, crits, with_ssim
+        sums_op, _, tail = _LossSums._ops(aux, crits)
+        sums = sums_op(sr_c, hr_c, aux, K, *tail)
+        if with_ssim:
+            return sums, ops.ssim(sr_c, hr_c).mean()
+        return sums
 
     @staticmethod
-    def backward(ctx, dsums, dS):
+    def backward(ctx, dsums, dS=None):
         from . import ops
         sr, hr, aux = ctx.saved_tensors
-        dsr = (ops.loss_bwd_soft if ctx.soft else ops.loss_bwd)(sr, hr, aux, dsums.contiguous(), ctx.K)
-        ops.ssim_bwd(sr, hr, _dscale(dS), out=dsr, accumulate=True)
-        return dsr, None, None, None, None
+        _, bwd_op, tail = _LossSums._ops(aux, ctx.crits)
+        dsr = bwd_op(sr, hr, aux, dsums.contiguous(), ctx.K, *tail)
+        if ctx.with_ssim:
+            ops.ssim_bwd(sr, hr, _dscale(dS), out=dsr, accumulate=True)
+        return dsr, None, None, None, None, None
 
 
 class SSIMLoss(torch.nn.Module):
@@ -180,65 +166,6 @@ class SSIMLoss(torch.nn.Module):
         return ssim_torch(img1, img2)
 
 
-def fused_losses(sr, hr, mask_list, trainable_weight, pixel_weight, dynamic_weight, group=None, with_ssim=False):
-    """l_pix and l_dynamic from one pass over (sr, hr) on the GPU: the region-byte kernels when the masks are one-hot, the
-    soft-mask kernels when they are not (contiguous fp32 CUDA masks of at most 16 regions that need no gradient), or None
-    for anything else (the caller then uses the PyTorch formulation; that includes every mask tensor of more than 16
-    regions, one-hot or not, which dasr_mask_compress used to reject with an error from here).  Same values and gradients as nn.L1Loss +
-    dynamic_weight_mask_loss('smoothl1'); with a process group the region sums are made global first.
-    ``with_ssim`` (the caller has checked ``SSIMLoss.hip_ok(sr, hr)``): the SSIM criterion of (sr, hr) rides along - in
-    the same autograd node, and its value in the same collective - and the result has two more entries: S with its
-    gradient, and its detached global value (the mean of the ranks' means: every rank's batch has the same size)."""
-    from . import ops
-    if not sr.is_cuda or sr.dtype != torch.float32 or mask_list.shape[2] == 0:
-        return None
-    H, W = sr.shape[2:]
-    h, w = mask_list.shape[2:]
-    if H % h or W % w or H // h != W // w:
-        return None
-    from . import graph, prep
-    K = mask_list.shape[1]
-    if K > ops.LOSS_MAX_REGIONS:              # beyond the kernels (and beyond dasr_mask_compress): nothing to classify
-        return None
-    S = None
-    if prep.attach_region(mask_list):         # no-op for masks from prep.depth_to_masks / already classified
-        if with_ssim:
-            sums, S = _RegionSumsSSIM.apply(sr, hr, graph.attached_region(mask_list), K, False)
-        else:
-            sums = _RegionSums.apply(sr, hr, graph.attached_region(mask_list), K)
-    elif (mask_list.is_cuda and mask_list.dtype == torch.float32 and mask_list.is_contiguous()
-          and not mask_list.requires_grad):
-        if with_ssim:
-            sums, S = _RegionSumsSSIM.apply(sr, hr, mask_list, K, True)
-        else:
-            sums = _RegionSumsSoft.apply(sr, hr, mask_list, K)
-    else:
-        return None
-    num, den, l1 = sums[:K], sums[K:2 * K].detach(), sums[2 * K]
-    world = _world(group)
-    l_pix = pixel_weight * l1 / sr.numel()
-    l_pix_global = l_pix.detach()
-    S_global = S.detach() if with_ssim else None
-    if world > 1:
-        # ONE collective for everything the step needs from the other ranks' losses: K numerators | K denominators | L1 sum
-        # (| S when the SSIM criterion is on)
-        g = torch.cat([sums.detach(), S.detach().reshape(1)]) if with_ssim else sums.detach().clone()
-        torch.distributed.all_reduce(g, group=group)
-        gnum, gden = g[:K], g[K:2 * K]
-        local = num / gden * world
-        per = gnum / gden + (local - local.detach())
-        l_pix_global = pixel_weight * g[2 * K] / (sr.numel() * world)
-        if with_ssim:
-            S_global = g[2 * K + 1] / world
-    else:
-        per = num / den
-    sm = F.softmax(trainable_weight, dim=0)
-    l_dyn = (sm * per).sum() * dynamic_weight
-    if with_ssim:
-        return l_pix, l_dyn, per, sm, l_pix_global, S, S_global
-    return l_pix, l_dyn, per, sm, l_pix_global
-
-
 PIXEL_CRITERIA = ("l1", "l2", "cb")               # train.pixel_criterion (F_model_depthCond.py:50-58)
 REGION_CRITERIA = ("l1", "l2", "smoothl1")        # dynamic_loss.dynamic_criterion / mask_loss.mask_criterion (mask_loss.py)
 CB_EPS = 1e-6                                     # CharbonnierLoss(eps) (loss.py:40)
@@ -256,35 +183,6 @@ def check_criteria(pixel_criterion, dynamic_criterion, mask_criterion):
                                       % what)
         if c is not None and c not in REGION_CRITERIA:
             raise NotImplementedError("Loss type [%s] for depth loss is not recognized." % (c,))
-
-
-class _CritSums(torch.autograd.Function):
-    """sums = (K numerators of criterion A | K areas | pixel-criterion sum [| K numerators of criterion B]) in ONE pass over
-    sr, hr (dasr_loss_sums_crit / dasr_loss_sums_soft_crit) and one elementwise backward (dasr_loss_bwd[_soft]_crit).
-    ``aux``: region bytes (uint8) or float masks; ``crits`` = (pixel, A, B or None).  ``with_ssim``: a second output, the
-    SSIM criterion of (sr, hr), whose backward adds into the same dsr (as in _RegionSumsSSIM)."""
-
-    @staticmethod
-    def forward(ctx, sr, hr, aux, K, crits, with_ssim):
-        from . import ops
-        sr_c, hr_c = sr.contiguous(), hr.contiguous()
-        if aux.dtype != torch.uint8:
-            aux = aux.detach().contiguous()
-        ctx.save_for_backward(sr_c, hr_c, aux)
-        ctx.K, ctx.crits, ctx.with_ssim = K, crits, with_ssim
-        sums = ops.loss_sums_crit(sr_c, hr_c, aux, K, *crits)
-        if with_ssim:
-            return sums, ops.ssim(sr_c, hr_c).mean()
-        return sums
-
-    @staticmethod
-    def backward(ctx, dsums, dS=None):
-        from . import ops
-        sr, hr, aux = ctx.saved_tensors
-        dsr = ops.loss_bwd_crit(sr, hr, aux, dsums.contiguous(), ctx.K, *ctx.crits)
-        if ctx.with_ssim:
-            ops.ssim_bwd(sr, hr, _dscale(dS), out=dsr, accumulate=True)
-        return dsr, None, None, None, None, None
 
 
 def _pixel_sum(d, pixel_criterion):
@@ -323,9 +221,11 @@ def criterion_sums_torch(sr, hr, mask_list, pixel_criterion, crit_a, crit_b=None
 
 
 def _criterion_aux(sr, mask_list):
-    """What the ``_crit`` kernels read beside sr / hr - region bytes for one-hot masks, the masks themselves when they are
-    soft - or None where ``fused_losses`` would return None (CPU tensors, more than 16 regions, masks that need a gradient,
-    HR / LR sizes that are no integer scale)."""
+    """THE rule for when the loss kernels take a step's tensors.  What they read beside sr / hr - region bytes for one-hot
+    masks, the masks themselves when they are soft (contiguous fp32 CUDA masks that need no gradient) - or None: CPU
+    tensors, other dtypes, HR / LR sizes that are no integer scale, masks that need a gradient, and every mask tensor of more
+    than 16 regions, one-hot or not (checked before the masks are classified: dasr_mask_compress takes no more either).  On
+    None the caller uses the PyTorch formulation."""
     from . import graph, ops, prep
     if not sr.is_cuda or sr.dtype != torch.float32 or mask_list.shape[2] == 0:
         return None
@@ -333,18 +233,91 @@ def _criterion_aux(sr, mask_list):
     h, w = mask_list.shape[2:]
     if H % h or W % w or H // h != W // w or mask_list.shape[1] > ops.LOSS_MAX_REGIONS:
         return None
-    if prep.attach_region(mask_list):
+    if prep.attach_region(mask_list):         # no-op for masks from prep.depth_to_masks / already classified
         return graph.attached_region(mask_list)
     if mask_list.is_cuda and mask_list.dtype == torch.float32 and mask_list.is_contiguous() and not mask_list.requires_grad:
         return mask_list
     return None
 
 
+def _compose_losses(sums, S, N, K, crits, trainable_weight, pixel_weight, dynamic_weight, mask_criterion, mask_weight,
+                    mask_index, group):
+    """Everything after the sums, for every combination of criteria: ``sums`` in the kernels' layout for ``crits`` = (pixel,
+    A, B or None) with its gradient, ``S`` the SSIM value or None, ``N = sr.numel()``.  ``dynamic_weight`` None: no dynamic
+    term (A is then the static mask term's criterion); ``mask_criterion`` None: no static mask term.  More than one rank:
+    ONE collective carries every sum (and S); see ``criterion_losses`` for what is global and what stays local.  Returns the
+    dict of ``criterion_losses`` without 'fused', and the softmax of the trainable weights (None without a dynamic term)."""
+    pixel_criterion, crit_a, crit_b = crits
+    world = _world(group)
+    g = sums.detach()
+    S_log = None if S is None else S.detach()
+    if world > 1:
+        g = torch.cat([g, S_log.reshape(1)]) if S is not None else g.clone()
+        torch.distributed.all_reduce(g, group=group)
+        if S is not None:
+            S_log = g[-1] / world
+    px = sums[2 * K]
+    l_pix = pixel_weight * px * world if pixel_criterion == "cb" else pixel_weight * px / N
+    if world > 1:
+        l_pix_log = pixel_weight * g[2 * K] if pixel_criterion == "cb" else pixel_weight * g[2 * K] / (N * world)
+    else:
+        l_pix_log = l_pix.detach()
+    den, gden = sums[K:2 * K].detach(), g[K:2 * K]
+
+    def per_region(num, gnum, criterion, local_only):
+        if criterion == "smoothl1":
+            if world > 1 and not local_only:
+                # value = global ratio; gradient: this rank's numerator over the global denominator, times world so that
+                # the later gradient AVERAGE over ranks equals the gradient of the global loss
+                local = num / gden * world
+                return gnum / gden + (local - local.detach())
+            return num / den
+        if world > 1 and not local_only:
+            local = num / N
+            return gnum / (N * world) + (local - local.detach())
+        return num / N
+
+    out = dict(l_pix=l_pix, l_pix_log=l_pix_log, l_dyn=None, l_mask=None, per=None, S=S, S_log=S_log)
+    sm = None
+    if dynamic_weight is not None:
+        assert K == trainable_weight.numel(), "dynamic loss: %d trainable region weights but %d mask channels" % (trainable_weight.numel(), K)
+        out["per"] = per = per_region(sums[:K], g[:K], crit_a, False)
+        sm = F.softmax(trainable_weight, dim=0)
+        out["l_dyn"] = (sm * per).sum() * dynamic_weight
+    if mask_criterion is not None:
+        lo = 2 * K + 1 if crit_b is not None else 0
+        per_m = per_region(sums[lo:lo + K], None, mask_criterion, True)
+        out["l_mask"] = mask_weight * per_m.index_select(0, mask_index).squeeze(0)
+    return out, sm
+
+
+def fused_losses(sr, hr, mask_list, trainable_weight, pixel_weight, dynamic_weight, group=None, with_ssim=False):
+    """The default combination's l_pix and l_dynamic from one pass over (sr, hr) on the GPU, through the kernels that have
+    its criteria compiled in: the region-byte kernels when the masks are one-hot, the soft-mask kernels when they are not,
+    or None where ``_criterion_aux`` gives None (the caller then uses the PyTorch formulation).  Same values and gradients
+    as nn.L1Loss + dynamic_weight_mask_loss('smoothl1'); with a process group the region sums are made global first.
+    ``with_ssim`` (the caller has checked ``SSIMLoss.hip_ok(sr, hr)``): the SSIM criterion of (sr, hr) rides along - in
+    the same autograd node, and its value in the same collective - and the result has two more entries: S with its
+    gradient, and its detached global value (the mean of the ranks' means: every rank's batch has the same size).
+    Returns ``(l_pix, l_dyn, per, softmax(trainable_weight), global l_pix[, S, global S])``."""
+    aux = _criterion_aux(sr, mask_list)
+    if aux is None:
+        return None
+    K = mask_list.shape[1]
+    sums = _LossSums.apply(sr, hr, aux, K, None, with_ssim)
+    sums, S = sums if with_ssim else (sums, None)
+    t, sm = _compose_losses(sums, S, sr.numel(), K, ("l1", "smoothl1", None), trainable_weight, pixel_weight,
+                            dynamic_weight, None, None, None, group)
+    out = (t["l_pix"], t["l_dyn"], t["per"], sm, t["l_pix_log"])
+    return out + (S, t["S_log"]) if with_ssim else out
+
+
 def criterion_losses(sr, hr, mask_list, trainable_weight, pixel_weight=1.0, dynamic_weight=10.0, pixel_criterion="l1",
                      dynamic_criterion="smoothl1", mask_criterion=None, mask_weight=1.0, mask_index=None, group=None,
                      ssim=None, force_torch=False):
-    """The loss terms of a step for ANY combination of the reference's criteria (``fused_losses`` stays what the default
-    combination runs).  Values follow the reference, oddities included:
+    """The loss terms of a step for ANY combination of the reference's criteria, through the kernels that take the criteria
+    as arguments (the default combination's own step goes through ``fused_losses``: the same loops with its criteria compiled
+    in, the same arithmetic after them).  Values follow the reference, oddities included:
 
     * pixel: 'l1' / 'l2' are means over all elements, 'cb' is the SUM of sqrt(d^2 + 1e-6) (loss.py:46), each times
       ``pixel_weight``;
@@ -356,7 +329,7 @@ def criterion_losses(sr, hr, mask_list, trainable_weight, pixel_weight=1.0, dyna
       anyway; a second set of sums is computed only when ``mask_criterion != dynamic_criterion``.
 
     Fused path (one ``_crit`` pass forward, one backward; the SSIM criterion ``ssim`` rides in the node when its kernels take
-    the tensors) under the rule of ``fused_losses``; otherwise - and with ``force_torch`` - ``criterion_sums_torch``.  With
+    the tensors) under the rule of ``_criterion_aux``; otherwise - and with ``force_torch`` - ``criterion_sums_torch``.  With
     both region terms off the pixel criterion is one PyTorch expression and no kernel runs.
 
     More than one rank: ONE collective carries every sum (and S).  The logged pixel value is the global batch's; 'smoothl1'
@@ -371,57 +344,21 @@ def criterion_losses(sr, hr, mask_list, trainable_weight, pixel_weight=1.0, dyna
     dyn_on, mask_on = dynamic_weight is not None, mask_criterion is not None
     crit_a = dynamic_criterion if dyn_on else mask_criterion
     crit_b = mask_criterion if dyn_on and mask_on and mask_criterion != dynamic_criterion else None
+    crits = (pixel_criterion, crit_a, crit_b)
     K = mask_list.shape[1] if crit_a is not None else 0
-    N = sr.numel()
-    world = _world(group)
     S = None
     aux = None if force_torch or crit_a is None else _criterion_aux(sr, mask_list)
     if aux is not None:
-        crits = (pixel_criterion, crit_a, crit_b)
-        if ssim is not None and ssim.hip_ok(sr, hr):
-            sums, S = _CritSums.apply(sr, hr, aux, K, crits, True)
-        else:
-            sums = _CritSums.apply(sr, hr, aux, K, crits, False)
+        with_ssim = ssim is not None and ssim.hip_ok(sr, hr)
+        sums = _LossSums.apply(sr, hr, aux, K, crits, with_ssim)
+        sums, S = sums if with_ssim else (sums, None)
     else:
-        sums = criterion_sums_torch(sr, hr, mask_list, pixel_criterion, crit_a, crit_b)
+        sums = criterion_sums_torch(sr, hr, mask_list, *crits)
     if ssim is not None and S is None:
         S = ssim(sr, hr)
-    g = sums.detach()
-    S_log = None if S is None else S.detach()
-    if world > 1:
-        g = torch.cat([g, S_log.reshape(1)]) if S is not None else g.clone()
-        torch.distributed.all_reduce(g, group=group)
-        if S is not None:
-            S_log = g[-1] / world
-    px, gpx = sums[2 * K], g[2 * K]
-    if pixel_criterion == "cb":
-        l_pix, l_pix_log = pixel_weight * px * world, pixel_weight * gpx
-    else:
-        l_pix, l_pix_log = pixel_weight * px / N, pixel_weight * gpx / (N * world)
-    den, gden = sums[K:2 * K].detach(), g[K:2 * K]
-
-    def per_region(num, gnum, criterion, local_only):
-        if criterion == "smoothl1":
-            if world > 1 and not local_only:
-                local = num / gden * world
-                return gnum / gden + (local - local.detach())
-            return num / den
-        if world > 1 and not local_only:
-            local = num / N
-            return gnum / (N * world) + (local - local.detach())
-        return num / N
-
-    out = dict(l_pix=l_pix, l_pix_log=l_pix_log.detach(), l_dyn=None, l_mask=None, per=None, S=S, S_log=S_log,
-               fused=aux is not None)
-    if dyn_on:
-        assert K == trainable_weight.numel(), "dynamic loss: %d trainable region weights but %d mask channels" % (trainable_weight.numel(), K)
-        per = per_region(sums[:K], g[:K], dynamic_criterion, False)
-        out["per"] = per
-        out["l_dyn"] = (F.softmax(trainable_weight, dim=0) * per).sum() * dynamic_weight
-    if mask_on:
-        lo = 2 * K + 1 if crit_b is not None else 0
-        per_m = per_region(sums[lo:lo + K], None, mask_criterion, True)
-        out["l_mask"] = mask_weight * per_m.index_select(0, mask_index).squeeze(0)
+    out, _ = _compose_losses(sums, S, sr.numel(), K, crits, trainable_weight, pixel_weight, dynamic_weight, mask_criterion,
+                             mask_weight, mask_index, group)
+    out["fused"] = aux is not None
     return out
 
 
@@ -519,9 +456,12 @@ class Trainer:
         check_criteria(pixel_criterion, dynamic_criterion, mask_criterion)
         self.pixel_criterion, self.dynamic_criterion, self.mask_criterion = pixel_criterion, dynamic_criterion, mask_criterion
         self.l_mask_w = float(mask_weight)
-        # the default combination keeps the step it always had (_losses: fused_losses / DynamicMaskLoss)
+        # the default combination keeps the terms it always had (_losses: fused_losses / DynamicMaskLoss) and the order in
+        # which its step adds them; any other adds in the reference's order (F_model_depthCond.py:163-190)
         self._default_criteria = (pixel_criterion == "l1" and dynamic_criterion == "smoothl1" and mask_criterion is None
                                   and dynamic_weight is not None)
+        self._term_order = (("l_pix", "l_dynamic", "l_ssim") if self._default_criteria
+                            else ("l_pix", "l_ssim", "l_mask", "l_dynamic"))
         self.dynamic_loss = None if dynamic_weight is None else DynamicMaskLoss(num_regions, dynamic_weight).to(device)
         self.mask_region = None
         self._mask_idx = None if mask_criterion is None else torch.zeros(1, dtype=torch.int64, device=device)
@@ -684,64 +624,52 @@ class Trainer:
             from . import prep
             prep.attach_region(masks)          # before the step's work is queued; free for prep.depth_to_masks output
         sr = self.net(lq, depth, masks)
-        grp = self.group if self.world > 1 else None
-        if not self._default_criteria:
-            return self._finish_step(self._criteria_terms(sr, gt, masks, grp))
-        l_pix, l_dyn, l_pix_log, S, S_log = self._losses(sr, gt, masks, grp)
-        total = l_pix + l_dyn
-        if S is not None:
-            total = total + self.l_ssim_w * S
-        self._buckets, self._submitted = [], set()
-        total.backward()
-        self._finish_allreduce()
-        self.optimizer.step()
-        self.log = {"l_all": l_pix_log + l_dyn.detach(), "l_pix": l_pix_log, "l_dynamic": l_dyn.detach()}
-        if S is not None:
-            l_ssim = self.l_ssim_w * S_log
-            self.log["l_all"] = self.log["l_all"] + l_ssim
-            self.log["l_ssim"] = l_ssim
-        return self.log
+        return self._finish_step(self._losses(sr, gt, masks, self.group if self.world > 1 else None))
 
     force_torch_criteria = False  # tests: a non-default combination through the PyTorch formulation on the same tensors
 
-    def _criteria_terms(self, sr, gt, masks, grp):
-        dyn = self.dynamic_loss
-        return criterion_losses(sr, gt, masks, None if dyn is None else dyn.trainable_weight, self.l_pix_w,
-                                None if dyn is None else dyn.l_mask_w, self.pixel_criterion, self.dynamic_criterion,
-                                self.mask_criterion, self.l_mask_w, self._mask_idx, grp, self.ssim_loss,
-                                self.force_torch_criteria)
-
     def _finish_step(self, t):
-        """Backward, gradient exchange, Adam and the log of a step whose terms ``criterion_losses`` computed: l_pix, then
-        l_ssim, l_mask and l_dynamic for the criteria that are on, in the reference's order (F_model_depthCond.py:163-190)."""
-        total = t["l_pix"]
-        log = {"l_pix": t["l_pix_log"]}
-        if t["S"] is not None:
-            total = total + self.l_ssim_w * t["S"]
-            log["l_ssim"] = self.l_ssim_w * t["S_log"]
-        if t["l_mask"] is not None:
-            total = total + t["l_mask"]
-            log["l_mask"] = t["l_mask"].detach()
-        if t["l_dyn"] is not None:
-            total = total + t["l_dyn"]
-            log["l_dynamic"] = t["l_dyn"].detach()
+        """Backward, gradient exchange, Adam and the log of a step whose terms ``_losses`` computed, added in
+        ``self._term_order``."""
+        terms = {"l_pix": ("l_pix", "l_pix_log"), "l_ssim": ("S", "S_log"), "l_mask": ("l_mask", "l_mask"),
+                 "l_dynamic": ("l_dyn", "l_dyn")}
+        total, log = None, {}
+        for key in self._term_order:
+            term, value = (t[k] for k in terms[key])
+            if term is None:
+                continue
+            if key == "l_ssim":
+                term, value = self.l_ssim_w * term, self.l_ssim_w * value
+            total = term if total is None else total + term
+            log[key] = value.detach()
         self._buckets, self._submitted = [], set()
         total.backward()
         self._finish_allreduce()
         self.optimizer.step()
-        log["l_all"] = sum(log.values())
+        l_all = None
+        for value in log.values():
+            l_all = value if l_all is None else l_all + value
+        log["l_all"] = l_all
         self.log = log
         return self.log
 
     def _losses(self, sr, gt, masks, grp):
-        """``(l_pix, l_dyn, l_pix_log, S, S_log)`` of a step: the loss terms with their gradients, the global-batch L1
-        value for the log, and - None, None with the SSIM criterion off - S with its gradient and its global value.  On the
-        HIP path S shares the fused losses' autograd node and collective; otherwise it is a term of its own (``SSIMLoss``)
-        whose value rides with the L1 value in the dynamic loss's collective."""
+        """The terms of a step, as the dict of ``criterion_losses``: ``l_pix`` / ``l_dyn`` / ``l_mask`` / ``S`` with their
+        gradients (None for a term that is off), ``l_pix_log`` / ``S_log`` the global-batch values for the log.  Any
+        combination but the default is ``criterion_losses``.  The default one is ``fused_losses`` - on the HIP path S
+        shares the fused losses' autograd node and collective - and where that returns None, ``F.l1_loss`` +
+        ``DynamicMaskLoss``, with S a term of its own (``SSIMLoss``) whose value rides with the L1 value in the dynamic
+        loss's collective."""
+        dyn = self.dynamic_loss
+        if not self._default_criteria:
+            return criterion_losses(sr, gt, masks, None if dyn is None else dyn.trainable_weight, self.l_pix_w,
+                                    None if dyn is None else dyn.l_mask_w, self.pixel_criterion, self.dynamic_criterion,
+                                    self.mask_criterion, self.l_mask_w, self._mask_idx, grp, self.ssim_loss,
+                                    self.force_torch_criteria)
         on = self.ssim_loss is not None
         hip = on and self.ssim_loss.hip_ok(sr, gt)
-        fused = fused_losses(sr, gt, masks, self.dynamic_loss.trainable_weight, self.l_pix_w, self.dynamic_loss.l_mask_w,
-                             grp, **({"with_ssim": True} if hip else {}))
+        fused = fused_losses(sr, gt, masks, dyn.trainable_weight, self.l_pix_w, dyn.l_mask_w, grp,
+                             **({"with_ssim": True} if hip else {}))
         S = S_log = None
         if fused is not None:
             l_pix, l_dyn, l_pix_log = fused[0], fused[1], fused[4]
@@ -754,15 +682,15 @@ class Trainer:
                     S_log = S_log.clone()
                     torch.distributed.all_reduce(S_log, group=grp)
                     S_log = S_log / self.world
-            return l_pix, l_dyn, l_pix_log, S, S_log
-        l_pix = self.l_pix_w * F.l1_loss(sr, gt)
-        if on:
-            S = self.ssim_loss(sr, gt)
-        piggyback = l_pix.detach() if S is None else torch.stack([l_pix.detach(), S.detach()])
-        per, weighted, l_dyn, sm = self.dynamic_loss(sr, gt, masks, grp, piggyback=piggyback)
-        glob = self.dynamic_loss.piggyback_sum / self.world              # the global-batch values
-        l_pix_log, S_log = (glob, None) if S is None else glob.unbind(0)
-        return l_pix, l_dyn, l_pix_log, S, S_log
+        else:
+            l_pix = self.l_pix_w * F.l1_loss(sr, gt)
+            if on:
+                S = self.ssim_loss(sr, gt)
+            piggyback = l_pix.detach() if S is None else torch.stack([l_pix.detach(), S.detach()])
+            per, weighted, l_dyn, sm = dyn(sr, gt, masks, grp, piggyback=piggyback)
+            glob = dyn.piggyback_sum / self.world                        # the global-batch values
+            l_pix_log, S_log = (glob, None) if S is None else glob.unbind(0)
+        return dict(l_pix=l_pix, l_pix_log=l_pix_log, l_dyn=l_dyn, l_mask=None, S=S, S_log=S_log)
 
     @torch.no_grad()
     def test(self, lq, depth, masks):

@@ -839,100 +839,66 @@ def region_pool_bwd(dout, maskr, area, feat_shape):
     return dfeat
 
 
-# ---- harness losses (one-hot masks) ------------------------------------------------------------
-def loss_sums(sr, hr, region, K):
+# ---- harness losses: csrc/loss.hip, one kernel family with two criterion policies ------------------------------------
+LOSS_MAX_REGIONS = 16
+CRIT_CODES = {"l1": 0, "l2": 1, "cb": 2, "smoothl1": 3}       # DASR_CRIT_*; None -> DASR_CRIT_NONE
+
+
+def _loss_dims(sr, hr, aux, K):
+    """``aux``: region bytes [B,h,w] (uint8, dasr_mask_compress) or float masks [B,K,h,w]; -> (soft, aux pointer, B, C, h,
+    w, scale) of an integer HR / LR scale."""
     B, C, H, W = sr.shape
-    _, h, w = region.shape
+    soft = aux.dtype != torch.uint8
+    h, w = aux.shape[-2:]
     scale = H // h
-    assert H == h * scale and W == w * scale
-    sums = empty((2 * K + 1,), sr)
-    _call("dasr_loss_sums", _p(sr), _p(hr), _lib.ptr(region, dtype=torch.uint8), _p(sums), B, C, h, w, scale, K)
-    return sums
+    assert hr.shape == sr.shape and aux.shape[:-2] == ((B, K) if soft else (B,)) and H == h * scale and W == w * scale
+    return soft, _p(aux) if soft else _lib.ptr(aux, dtype=torch.uint8), B, C, h, w, scale
+
+
+def _loss_call(name, sr, hr, aux, dsums, K, crits=None):
+    """One of the eight entry points dasr_loss_{sums,bwd}[_soft][_crit]: ``dsums`` None - the sums; otherwise dsr.
+    ``crits`` None: the fixed policy (pixel l1, region smooth-L1); (pixel, A, B or None): the criteria as arguments."""
+    soft, aux_p, B, C, h, w, scale = _loss_dims(sr, hr, aux, K)
+    nsums = (2 if crits is None or crits[2] is None else 3) * K + 1
+    codes = () if crits is None else tuple(-1 if c is None else CRIT_CODES[c] for c in crits)
+    if dsums is None:
+        out, mid = empty((nsums,), sr), ()
+    else:
+        assert dsums.numel() == nsums
+        out, mid = torch.empty_like(sr), (_p(dsums),)
+    _call("dasr_loss_" + name + ("_soft" if soft else "") + ("" if crits is None else "_crit"), _p(sr), _p(hr), aux_p, *mid,
+          _p(out), B, C, h, w, scale, K, *codes)
+    return out
+
+
+def loss_sums(sr, hr, region, K):
+    """K smooth-L1 numerators | K areas | sum|sr-hr| for region bytes [B,h,w] (dasr_loss_sums)."""
+    return _loss_call("sums", sr, hr, region, None, K)
 
 
 def loss_bwd(sr, hr, region, dsums, K):
-    B, C, H, W = sr.shape
-    _, h, w = region.shape
-    dsr = torch.empty_like(sr)
-    _call("dasr_loss_bwd", _p(sr), _p(hr), _lib.ptr(region, dtype=torch.uint8), _p(dsums), _p(dsr), B, C, h, w, H // h, K)
-    return dsr
-
-
-# ---- harness losses (soft masks: any float values) ---------------------------------------------
-LOSS_MAX_REGIONS = 16
-
-
-def _soft_loss_dims(sr, mask, K):
-    B, C, H, W = sr.shape
-    Bm, Km, h, w = mask.shape
-    scale = H // h
-    assert (Bm, Km) == (B, K) and H == h * scale and W == w * scale
-    return B, C, h, w, scale
+    return _loss_call("bwd", sr, hr, region, dsums, K)
 
 
 def loss_sums_soft(sr, hr, mask, K):
     """K numerators sum smooth_l1(M_k (sr-hr)) | K areas | sum|sr-hr| for float masks [B,K,h,w] (dasr_loss_sums_soft)."""
-    B, C, h, w, scale = _soft_loss_dims(sr, mask, K)
-    assert hr.shape == sr.shape
-    sums = empty((2 * K + 1,), sr)
-    _call("dasr_loss_sums_soft", _p(sr), _p(hr), _p(mask), _p(sums), B, C, h, w, scale, K)
-    return sums
+    return _loss_call("sums", sr, hr, mask, None, K)
 
 
 def loss_bwd_soft(sr, hr, mask, dsums, K):
-    B, C, h, w, scale = _soft_loss_dims(sr, mask, K)
-    assert hr.shape == sr.shape and dsums.numel() == 2 * K + 1
-    dsr = torch.empty_like(sr)
-    _call("dasr_loss_bwd_soft", _p(sr), _p(hr), _p(mask), _p(dsums), _p(dsr), B, C, h, w, scale, K)
-    return dsr
-
-
-# ---- harness losses with the criteria as arguments (region bytes or soft masks) ------------------
-CRIT_CODES = {"l1": 0, "l2": 1, "cb": 2, "smoothl1": 3}       # DASR_CRIT_*; None -> DASR_CRIT_NONE
-
-
-def _crit_args(pixel, crit_a, crit_b):
-    return CRIT_CODES[pixel], CRIT_CODES[crit_a], -1 if crit_b is None else CRIT_CODES[crit_b]
-
-
-def _crit_dims(sr, aux, K):
-    """``aux``: region bytes [B,h,w] (uint8, dasr_mask_compress) or float masks [B,K,h,w]; -> (soft, B, C, h, w, scale)."""
-    if aux.dtype == torch.uint8:
-        B, C, H, W = sr.shape
-        _, h, w = aux.shape
-        scale = H // h
-        assert aux.shape[0] == B and H == h * scale and W == w * scale
-        return False, B, C, h, w, scale
-    return (True,) + _soft_loss_dims(sr, aux, K)
+    return _loss_call("bwd", sr, hr, mask, dsums, K)
 
 
 def loss_sums_crit(sr, hr, aux, K, pixel, crit_a, crit_b=None):
     """K numerators of criterion A | K areas | the pixel criterion's sum | with ``crit_b``: K numerators of criterion B
     (dasr_loss_sums_crit / dasr_loss_sums_soft_crit).  ``pixel``: 'l1' | 'l2' | 'cb'; ``crit_a`` / ``crit_b``:
     'l1' | 'l2' | 'smoothl1'."""
-    soft, B, C, h, w, scale = _crit_dims(sr, aux, K)
-    assert hr.shape == sr.shape
-    sums = empty(((2 if crit_b is None else 3) * K + 1,), sr)
-    if soft:
-        _call("dasr_loss_sums_soft_crit", _p(sr), _p(hr), _p(aux), _p(sums), B, C, h, w, scale, K, *_crit_args(pixel, crit_a, crit_b))
-    else:
-        _call("dasr_loss_sums_crit", _p(sr), _p(hr), _lib.ptr(aux, dtype=torch.uint8), _p(sums), B, C, h, w, scale, K,
-              *_crit_args(pixel, crit_a, crit_b))
-    return sums
+    return _loss_call("sums", sr, hr, aux, None, K, (pixel, crit_a, crit_b))
 
 
 def loss_bwd_crit(sr, hr, aux, dsums, K, pixel, crit_a, crit_b=None):
     """dsr from the device vector ``dsums`` (the layout of loss_sums_crit's result; the areas' entries are not read)."""
-    soft, B, C, h, w, scale = _crit_dims(sr, aux, K)
-    assert hr.shape == sr.shape and dsums.numel() == (2 if crit_b is None else 3) * K + 1
-    dsr = torch.empty_like(sr)
-    if soft:
-        _call("dasr_loss_bwd_soft_crit", _p(sr), _p(hr), _p(aux), _p(dsums), _p(dsr), B, C, h, w, scale, K,
-              *_crit_args(pixel, crit_a, crit_b))
-    else:
-        _call("dasr_loss_bwd_crit", _p(sr), _p(hr), _lib.ptr(aux, dtype=torch.uint8), _p(dsums), _p(dsr), B, C, h, w, scale, K,
-              *_crit_args(pixel, crit_a, crit_b))
-    return dsr
+    return _loss_call("bwd", sr, hr, aux, dsums, K, (pixel, crit_a, crit_b))
 
 
 # ---- SSIM: validation metric and training criterion (csrc/ssim.hip, csrc/ssim_bwd.hip) ----------

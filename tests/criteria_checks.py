@@ -72,6 +72,12 @@ def make_inputs(s, K, kind, dyadic=False):
         masks[torch.rand(masks.shape, generator=gen) < 0.3] = 0.0
         if kind.endswith("_empty"):
             masks[:, K - 1] = 0.0
+        if dyadic:
+            # multiples of 1/2: u = M d is a multiple of 1/32 and every smooth-L1 term one of 2^-11, so a region's
+            # numerator (terms >= 0: no partial sum exceeds it) is exact in fp32 in any order while it stays below 2^13
+            masks = torch.round(masks * 2) / 2
+            u = F.interpolate(masks, scale_factor=s, mode="nearest").double().unsqueeze(2) * (sr - hr).double().unsqueeze(1)
+            assert F.smooth_l1_loss(u, torch.zeros_like(u), reduction="none").sum(dim=(0, 2, 3, 4)).max().item() < 2 ** 13
     if not kind.endswith("_empty"):
         assert masks.sum(dim=(0, 2, 3)).min().item() > 0.5, (s, K, kind)
     return sr, hr, masks.contiguous()
@@ -337,21 +343,23 @@ def check_crit_golden_case(device):
 
 
 def check_default_bits(device):
-    """(pixel l1, A smoothl1, no B) on region bytes: the new family's sums and dsr equal the existing kernels' bit for bit.
-    dsr on the general inputs; the sums on the dyadic ones, where the order in which the float atomics land cannot matter
-    (two launches of the SAME kernel differ in the last bits otherwise)."""
+    """(pixel l1, A smoothl1, no B), on region bytes and on soft masks: the argument-policy kernels' sums and dsr equal the
+    fixed-policy kernels' bit for bit.  dsr on the general inputs; the sums on the dyadic ones, where the order in which the
+    float atomics land cannot matter (two launches of the SAME kernel differ in the last bits otherwise)."""
     for s in SCALES:
         for K in KS:
             for dyadic in (False, True):
-                sr, hr, masks = make_inputs(s, K, "onehot", dyadic)
-                sr_d, hr_d, region = sr.to(device), hr.to(device), _aux(masks, "onehot", device)
-                if dyadic:
-                    new, old = ops.loss_sums_crit(sr_d, hr_d, region, K, "l1", "smoothl1"), ops.loss_sums(sr_d, hr_d, region, K)
-                    assert torch.equal(new, old), (s, K, new, old)
-                    assert float(old[2 * K]) > 0 and float(old[0]) > 0
-                dsums = _dsums(2 * K + 1, 3).float().to(device)
-                new, old = ops.loss_bwd_crit(sr_d, hr_d, region, dsums, K, "l1", "smoothl1"), ops.loss_bwd(sr_d, hr_d, region, dsums, K)
-                assert torch.equal(new, old), (s, K, dyadic)
+                for kind, sums_fn, bwd_fn in (("onehot", ops.loss_sums, ops.loss_bwd),
+                                              ("soft", ops.loss_sums_soft, ops.loss_bwd_soft)):
+                    sr, hr, masks = make_inputs(s, K, kind, dyadic)
+                    sr_d, hr_d, aux = sr.to(device), hr.to(device), _aux(masks, kind, device)
+                    if dyadic:
+                        new, old = ops.loss_sums_crit(sr_d, hr_d, aux, K, "l1", "smoothl1"), sums_fn(sr_d, hr_d, aux, K)
+                        assert torch.equal(new, old), (s, K, kind, new, old)
+                        assert float(old[2 * K]) > 0 and float(old[0]) > 0
+                    dsums = _dsums(2 * K + 1, 3).float().to(device)
+                    new, old = ops.loss_bwd_crit(sr_d, hr_d, aux, dsums, K, "l1", "smoothl1"), bwd_fn(sr_d, hr_d, aux, dsums, K)
+                    assert torch.equal(new, old), (s, K, kind, dyadic)
     return dict(ok=True)
 
 

@@ -390,7 +390,7 @@ def check_fused_loss(device):
         assert int(flag.item()) == 0
         sr_d = sr.clone().to(device).requires_grad_(True)
         w_d = w_o.detach().clone().to(device).requires_grad_(True)
-        sums = harness._RegionSums.apply(sr_d, gt.to(device), region, 10)
+        sums = harness._LossSums.apply(sr_d, gt.to(device), region, 10, None, False)
         num, den, l1 = sums[:10], sums[10:20].detach(), sums[20]
         l_pix = l1 / sr.numel()
         l_dyn = (F.softmax(w_d, 0) * (num / den)).sum() * 10.0

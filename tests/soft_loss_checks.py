@@ -1,5 +1,5 @@
 """Soft (non one-hot) depth masks in the fused loss and the captured training step (csrc/loss.hip: k_loss_sums_soft /
-k_loss_bwd_soft; harness._RegionSumsSoft, harness.fused_losses, harness.Trainer; prep.mark_soft).  Each check takes the
+k_loss_bwd_soft; harness._LossSums, harness.fused_losses, harness.Trainer; prep.mark_soft).  Each check takes the
 device ("cpu": the kernel emulator, "cuda": the MI355X); tests/test_soft_loss.py runs them.
 
 Gates of the loss values and gradients are the project's own for these quantities (parity_checks.check_fused_loss):
@@ -70,12 +70,12 @@ def _gate(got, want, K, what):
 
 
 def _soft_loss_on(device, B, h, w, s, K, kind):
-    """harness._RegionSumsSoft -> num / den, softmax, x 10, exactly as check_fused_loss does for the one-hot op."""
+    """harness._LossSums -> num / den, softmax, x 10, exactly as check_fused_loss does for the one-hot op."""
     from dasr_amd import harness
     sr, gt, masks, wts = make_inputs(B, h, w, s, K, kind)
     sr_d = sr.clone().to(device).requires_grad_(True)
     w_d = wts.clone().to(device).requires_grad_(True)
-    sums = harness._RegionSumsSoft.apply(sr_d, gt.to(device), masks.to(device), K)
+    sums = harness._LossSums.apply(sr_d, gt.to(device), masks.to(device), K, None, False)
     num, den, l1 = sums[:K], sums[K:2 * K].detach(), sums[2 * K]
     l_pix = l1 / sr.numel()
     l_dyn = (F.softmax(w_d, 0) * (num / den)).sum() * 10.0

@@ -5,8 +5,8 @@
 Without --worker this is the driver: it starts the GPU work as a child process under a time limit of its own
 (``timeout -k 10 <seconds>``) and stops if it fails.
 
-  default    (pixel l1, region smoothl1, no second criterion) through the new family against the existing kernels
-             (dasr_loss_sums / dasr_loss_bwd and their _soft twins): what the parametrisation costs.  Region bytes and soft
+  default    (pixel l1, region smoothl1, no second criterion) through the argument-policy kernels ("new") against the
+             fixed-policy ones ("existing": dasr_loss_sums / dasr_loss_bwd and their _soft twins): what the parametrisation costs.  Region bytes and soft
              masks; forward and backward; three windows of --iters launches a side, alternating, timed with device events.
              Achieved bytes/s against the algorithmic traffic (forward: read sr, hr; backward: read sr, hr, write dsr).
   criteria   each non-default combination, forward + backward, against the PyTorch formulation (criterion_sums_torch under
