@@ -73,6 +73,26 @@ def _side_stream(device, which="branch"):
         return _SIDE[key]
 
 
+def hand_over(event, *tensors):
+    """The ONE cross-stream hand-over: ``tensors`` were written on another stream, ``event`` was recorded there behind
+    their producer, the current stream is about to use them.  Waits for the event and tells the caching allocator that
+    the current stream uses each tensor - and the amax side-car that travels with it (ops.set_amax): both come from the
+    other stream's pool and would go back to it, for that stream's next allocation to write into, the moment the last
+    Python reference is dropped, however much work that reads them is still queued here.  No-op without an event (one
+    stream)."""
+    if event is None:
+        return
+    cur = torch.cuda.current_stream()
+    cur.wait_event(event)
+    for t in tensors:
+        if t is None or not t.is_cuda:
+            continue
+        t.record_stream(cur)
+        side_car = ops.get_amax(t)
+        if side_car is not None:
+            side_car.record_stream(cur)
+
+
 # ---------------------------------------------------------------------------------------------
 # recorded primitives
 # ---------------------------------------------------------------------------------------------
@@ -207,9 +227,7 @@ def pack(tape, v, g=None, transposed=False, dtype=torch.float32):
     def bwd():
         if out.grad is None:
             return
-        if out.grad_event is not None:
-            torch.cuda.current_stream().wait_event(out.grad_event)
-            out.grad.record_stream(torch.cuda.current_stream())
+        hand_over(out.grad_event, out.grad)
         dv, dg = ops.weight_pack_bwd(out.grad, v.data, g.data if g is not None else None, inv, transposed)
         out.grad = None
         accum(v, dv)
@@ -248,9 +266,7 @@ def pack_pair(tape, va, vb, dtype=torch.float32):
     def bwd():
         if out.grad is None:
             return
-        if out.grad_event is not None:
-            torch.cuda.current_stream().wait_event(out.grad_event)
-            out.grad.record_stream(torch.cuda.current_stream())
+        hand_over(out.grad_event, out.grad)
         da, _ = ops.weight_pack_bwd(out.grad, va.data, None, None, False, o_off=0)
         db, _ = ops.weight_pack_bwd(out.grad, vb.data, None, None, False, o_off=Oa)
         out.grad = None
@@ -284,9 +300,7 @@ def bias_pair(tape, ba, bb):
     def bwd():
         if out.grad is None:
             return
-        if out.grad_event is not None:
-            torch.cuda.current_stream().wait_event(out.grad_event)
-            out.grad.record_stream(torch.cuda.current_stream())
+        hand_over(out.grad_event, out.grad)
         g = out.grad
         out.grad = None
         accum(ba, g[:na])
@@ -332,7 +346,8 @@ def want_amax(tape, like, shape=None):
 
 
 def conv(tape, x, w, bias=None, *, stride=1, pad=1, transposed=False, act=ops.ACT_NONE, ps_r=1, residual=None,
-         side_wgrad=False, want_stats=False, out_dtype=None):
+         side_wgrad=False, want_stats=False, out_dtype=None, out_amax=True):
+    """``out_amax=False``: no consumer of the output is a split convolution (it feeds a SEAN): leave no max |y| behind."""
     stats = None
     f32 = x.data.dtype == torch.float32 and out_dtype in (None, torch.float32)
     if (want_stats and FUSE_INSTNORM_STATS and f32 and act == ops.ACT_NONE and ps_r == 1 and residual is None and
@@ -354,7 +369,7 @@ def conv(tape, x, w, bias=None, *, stride=1, pad=1, transposed=False, act=ops.AC
         if isinstance(w.split, tuple):
             y = ops.conv3x3_fwd_split2(x.data, _amax(x), w.split, bias.data if bias is not None else None, w.data.shape[4],
                                        residual.data if residual is not None else None, act, ps_r,
-                                       amax=want_amax(tape, x.data))
+                                       amax=want_amax(tape, x.data) if out_amax else None)
         else:
             y = ops.conv3x3_fwd_split(x.data, w.split, bias.data if bias is not None else None, w.data.shape[4],
                                       residual.data if residual is not None else None, act, ps_r)
@@ -398,9 +413,7 @@ def conv(tape, x, w, bias=None, *, stride=1, pad=1, transposed=False, act=ops.AC
             return
         dy = out.grad
         out.grad = None
-        if out.grad_event is not None:       # the gradient was produced on another stream
-            torch.cuda.current_stream().wait_event(out.grad_event)
-            dy.record_stream(torch.cuda.current_stream())
+        hand_over(out.grad_event, dy)        # the gradient (and its amax) was produced on another stream
         if not x.requires_grad and residual is None and ps_r == 1 and act != ops.ACT_NONE:
             # leaf layer (the depth-map branch): activation backward fused into the weight gradient
             dw, db = ops.conv2d_wgrad_act(x.data, dy, y, wshape, act, stride, pad, transposed,
@@ -438,8 +451,7 @@ def conv(tape, x, w, bias=None, *, stride=1, pad=1, transposed=False, act=ops.AC
                 if ws not in tape.side_streams:
                     tape.side_streams.append(ws)
                 with torch.cuda.stream(ws):
-                    ws.wait_event(ready)
-                    dconv.record_stream(ws)
+                    hand_over(ready, dconv)
                     dw, db = ops.conv2d_wgrad(x.data, dconv, wshape, stride, pad, transposed,
                                               want_bias=bias is not None)
                     done = ws.record_event()
@@ -571,9 +583,7 @@ def expand_s2(tape, wp):
     def bwd():
         if out.grad is None:
             return
-        if out.grad_event is not None:
-            torch.cuda.current_stream().wait_event(out.grad_event)
-            out.grad.record_stream(torch.cuda.current_stream())
+        hand_over(out.grad_event, out.grad)
         g = out.grad
         out.grad = None
         accum(wp, ops.weight_collapse_s2(g, Cin, Cout))
@@ -595,10 +605,8 @@ def expand_t2(tape, wp, bias):
         if wout.grad is None:
             return
         for v in (wout, bout):
-            if v is not None and v.grad_event is not None:
-                torch.cuda.current_stream().wait_event(v.grad_event)
-                if v.grad is not None:
-                    v.grad.record_stream(torch.cuda.current_stream())
+            if v is not None:
+                hand_over(v.grad_event, v.grad)
         gw, gb = wout.grad, (bout.grad if bout is not None else None)
         wout.grad = None
         if bout is not None:
@@ -671,16 +679,12 @@ def sean_mod(tape, t, gb2, mask, D, bias_g, bias_b, alpha_g, alpha_b, residual, 
     if residual is not None:
         residual.uses += 1
     if gb2.event is not None:                # gamma2/beta2 were computed on the side stream
-        torch.cuda.current_stream().wait_event(gb2.event)
-        gb2.data.record_stream(torch.cuda.current_stream())
         # Resized mask planes / region bytes were allocated on the side stream too (MaskPack.resized under
         # tape.on_stream) and are read HERE and in this node's backward.  Without the record their memory goes back to the
         # side stream's pool the moment the last SEAN's backward closure is dropped - while that backward may still be
         # queued - and the depth-branch backward that follows on the side stream allocates and writes into it (seen as a
         # wrong dD of the first depth block with half-resolution soft masks).
-        for m in (mask.planes, mask.region):
-            if m is not None and m.is_cuda:
-                m.record_stream(torch.cuda.current_stream())
+        hand_over(gb2.event, gb2.data, mask.planes, mask.region)
     mean, var = t.stats if t.stats is not None else ops.instnorm_stats(t.data)
     y = ops.sean_fwd(t.data, mean, var, gb2.data, mask.planes, mask.region, mask.flag, D.data, bias_g.data, bias_b.data,
                      alpha_g.data, alpha_b.data, residual.data if residual is not None else None, relu,
@@ -798,7 +802,8 @@ def sean_depth_branch(tape, P, pre, depth_map):
     actv = conv(tape, depth_map, w_m, P[pre + ".mlp_mask.0.bias"], act=ops.ACT_RELU, out_dtype=dt)
     w_gb = pack_pair(tape, P[pre + ".mlp_gamma_o.weight"], P[pre + ".mlp_beta_o.weight"], dt)
     b_gb = bias_pair(tape, P[pre + ".mlp_gamma_o.bias"], P[pre + ".mlp_beta_o.bias"])
-    return conv(tape, actv, w_gb, b_gb)
+    # (gamma2 | beta2 go to dasr_sean_fwd, which takes no amax: no buffer to allocate, fill and hand across streams)
+    return conv(tape, actv, w_gb, b_gb, out_amax=False)
 
 
 def sean(tape, P, pre, t, depth_map, mask, st, residual, relu, consts, gb2=None):
@@ -951,8 +956,7 @@ def _depthnet_forward(tape, P, cfg, consts, inp, depth_map, depth_mask, region, 
     branch = {}
     side = _side_stream(inp.device) if (SIDE_STREAM and inp.is_cuda and mask_pack is not None) else None
     if side is not None:
-        main = torch.cuda.current_stream()
-        side.wait_stream(main)
+        ready = torch.cuda.current_stream().record_event()
         feat_hw = {}
         hw = (x0.data.shape[1], x0.data.shape[2])
         for i in executed:                 # feature size seen by block i (upscale1 before nb-2, upscale2 before nb-1)
@@ -962,6 +966,12 @@ def _depthnet_forward(tape, P, cfg, consts, inp, depth_map, depth_mask, region, 
                 hw = (hw[0] * 2, hw[1] * 2)
             feat_hw[i] = hw
         with tape.on_stream(side):
+            # The branch reads the CALLER's depth map (forward and, in the mask layer's weight gradient, backward) and
+            # masks.  They come from the main stream's pool; a caller that passes temporaries (net(lq.to(dev), ...)) holds
+            # no reference, so the last backward closure of the branch drops the last one - while the kernels it just
+            # queued here have not run - and the head / encoder backward that follows on the main stream is handed the
+            # block (seen as wrong mlp_mask.0.weight gradients of the first depth block, in whole-suite runs only).
+            hand_over(ready, dm.data, mask_pack.planes, mask_pack.region)
             for i in executed:
                 name, kind, _ = plan[i]
                 if kind != "depth":
