@@ -13,11 +13,13 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 #ifdef DASR_HIPEMU
-// round-to-nearest-even on the bits (the emulator's inputs are finite; NaN handling is the device cast's business)
+// round-to-nearest-even on the bits; NaN stays NaN (quieted: the rounding increment must not carry a NaN's mantissa
+// into the exponent and sign), as the device cast leaves it
 static inline bf16_t dasr_f2bf(float f) {
     unsigned u;
     memcpy(&u, &f, 4);
-    u = (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) u = (u >> 16) | 0x40u;
+    else u = (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
     unsigned short h = (unsigned short)u;
     bf16_t r;
     memcpy(&r, &h, 2);

@@ -50,7 +50,7 @@ __global__ void k_clamp_to_nchw(const float* __restrict__ y, float* __restrict__
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         size_t p = i % HW, c = (i / HW) % C, b = i / ((size_t)C * HW);
         float v = y[(b * HW + p) * C + c];
-        out[i] = fminf(fmaxf(v, lo), hi);
+        out[i] = v != v ? v : fminf(fmaxf(v, lo), hi);  // torch.clamp keeps NaN (fmaxf / fminf return the other operand)
     }
 }
 __global__ void k_clamp_to_nchw_bwd(const float* __restrict__ dout, const float* __restrict__ y, float* __restrict__ dy,

@@ -114,7 +114,7 @@ __global__ void __launch_bounds__(256) k_sean_fwd(SeanGeom g, const T* __restric
         float xh = (ld1(t + p * g.C + c) - mu) * s;
         float o = xh * (1.f + gam) + bet;
         if (residual) o += ld1(residual + p * g.C + c);
-        if (relu) o = o > 0.f ? o : 0.f;
+        if (relu) o = o <= 0.f ? 0.f : o;               // F.relu: NaN stays NaN (`o > 0 ? o : 0` sent it to 0)
         st1(out + p * g.C + c, o);
     }
 }
@@ -612,8 +612,8 @@ __global__ void __launch_bounds__(256, HAS_RES ? DASR_SEAN_RES_OCC : 3) k_sean_f
                 o.w = (f.tv[u].w - mu.w) * sc.w * (1.f + a_g * g1.w + (1.f - a_g) * f.g2[u].w) + a_b * b1.w + (1.f - a_b) * f.b2[u].w;
                 if (HAS_RES) { o.x += f.rv[u].x; o.y += f.rv[u].y; o.z += f.rv[u].z; o.w += f.rv[u].w; }
                 if (RELU) {
-                    o.x = o.x > 0.f ? o.x : 0.f; o.y = o.y > 0.f ? o.y : 0.f;
-                    o.z = o.z > 0.f ? o.z : 0.f; o.w = o.w > 0.f ? o.w : 0.f;
+                    o.x = o.x <= 0.f ? 0.f : o.x; o.y = o.y <= 0.f ? 0.f : o.y;     // NaN stays NaN, as in F.relu
+                    o.z = o.z <= 0.f ? 0.f : o.z; o.w = o.w <= 0.f ? 0.f : o.w;
                 }
                 if (AMAX) om = dasr_amax4(om, o);     // (clamped / shadow lanes hold duplicates of stored values)
                 if (live && y < g.H && x < g.W) {
@@ -757,7 +757,7 @@ __global__ void __launch_bounds__(256, HAS_RES ? DASR_SEAN_RES_OCC : 3) k_sean_f
                     float o = (dasr_bf2f(f.tv[e]) - mu[e]) * sc[e] * (1.f + a_g * g1v[j] + (1.f - a_g) * dasr_bf2f(f.g2[e])) +
                               a_b * b1v[j] + (1.f - a_b) * dasr_bf2f(f.b2[e]);
                     if (HAS_RES) o += dasr_bf2f(f.rv[e]);
-                    if (RELU) o = o > 0.f ? o : 0.f;
+                    if (RELU) o = o <= 0.f ? 0.f : o;           // NaN stays NaN, as in F.relu
                     o8[e] = dasr_f2bf(o);
                 }
             }
@@ -1339,7 +1339,7 @@ __global__ void __launch_bounds__(256) k_sean_fwd_soft(SeanGeom g, const T* __re
                     const float xh = (tq[j] - muq[j]) * scq[j];
                     o[j] = xh * (1.f + gam) + bet;
                     if (HAS_RES) o[j] += rq[j];
-                    if (RELU) o[j] = o[j] > 0.f ? o[j] : 0.f;
+                    if (RELU) o[j] = o[j] <= 0.f ? 0.f : o[j];  // NaN stays NaN, as in F.relu
                 }
                 st4(out + p * g.C + c, make_float4(o[0], o[1], o[2], o[3]));
             }

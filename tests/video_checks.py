@@ -130,6 +130,22 @@ def check_emit_u8(device):
                         assert want.dtype == np.uint8
                         assert np.array_equal(got[b] if C == 3 else got[b, :, :, 0], want), (C, (B, H, W), lo, hi, mm, b)
                     cases += 1
+    # A NaN pixel: a uint8 cannot carry it.  The emit's first clamp is fminf(fmaxf(y, net_lo), net_hi), which returns net_lo
+    # for NaN, so the pixel leaves as the byte of a pixel that holds net_lo (ops.clamp_to_nchw, the float path, keeps the
+    # NaN as torch.clamp does).  NaNs in the scalar head, in the vector body and in the last element.
+    for (lo, hi), mm in (((0, 1), (0, 1)), ((-1, 1), (-1, 1)), ((0.25, 1), (0, 1))):
+        y = torch.from_numpy(gen.uniform(-1.3, 1.3, size=(1, 7, 9, 3)).astype(np.float32))
+        twin = y.clone()
+        for pos in (0, 1, 17, 100, y.numel() - 1):
+            y.view(-1)[pos] = float("nan")
+            twin.view(-1)[pos] = lo
+        for off_in in (0, 3):
+            got = ops.frame_emit_u8(_offset_view(y, off_in, device), lo, hi, mm, swap_rb=False).cpu()
+            want = ops.frame_emit_u8(_offset_view(twin, off_in, device), lo, hi, mm, swap_rb=False).cpu()
+            assert torch.equal(got, want), ("NaN pixel", lo, hi, mm, off_in)
+            byte = int(round((min(max(lo, mm[0]), mm[1]) - mm[0]) / (mm[1] - mm[0]) * 255.0))
+            assert got.view(-1)[[0, 1, 17, 100, y.numel() - 1]].tolist() == [byte] * 5, ("NaN pixel byte", lo, hi, mm, byte)
+            cases += 1
     y2 = torch.zeros((1, 4, 4, 2), device=device)
     o2 = torch.zeros((1, 4, 4, 2), dtype=torch.uint8, device=device)
     rc = _lib.get().dasr_frame_emit_u8(ops._p(y2), ops._pu8(o2), 1, 4, 4, 2, 0.0, 1.0, 0.0, 1.0, 1, _lib.stream())
