@@ -1074,3 +1074,63 @@ def batch_plane(x, window=None, origins=None, flags=None, allow_transpose=False,
                                             _lib.stream())
     _batch_check("dasr_batch_plane", rc)
     return out
+
+
+# ---- geometric self-ensemble inference (csrc/ensemble.hip) ---------------------------------------------------------------
+def _ensemble_outs(name, out, N, H, W, C, dtype, like):
+    """The two group buffers ``([4N,H,W,C], [4N,W,H,C])`` of an expand: the caller's, shape-checked, or new ones."""
+    shapes = ((4 * N, H, W, C), (4 * N, W, H, C))
+    if out is None:
+        return tuple(torch.empty(s, dtype=dtype, device=like.device) for s in shapes)
+    a, t = out
+    if tuple(a.shape) != shapes[0] or tuple(t.shape) != shapes[1]:
+        raise ValueError("dasr_amd: %s out has shapes %s / %s, expected %s / %s"
+                         % (name, tuple(a.shape), tuple(t.shape), shapes[0], shapes[1]))
+    drop_amax(a)
+    drop_amax(t)
+    return a, t
+
+
+def ensemble_expand(x, out=None):
+    """float32 or uint8 ``[N,H,W,C]`` (C in 1, 3) -> ``(a [4N,H,W,C], t [4N,W,H,C])``: the eight flip / transpose members
+    of the reference's test_x8 (dasr_ensemble_expand_f32 / _u8; member numbering and layout in include/dasr.h), a
+    bit-exact move.  ``out``: ``(a, t)`` buffers of those shapes to write into instead of new ones."""
+    if x.dtype not in (torch.float32, torch.uint8):
+        raise TypeError("dasr_amd: ensemble_expand takes float32 or uint8, got %s" % x.dtype)
+    if x.dim() != 4:
+        raise TypeError("dasr_amd: ensemble_expand takes [N,H,W,C], got %s" % (tuple(x.shape),))
+    N, H, W, C = x.shape
+    a, t = _ensemble_outs("ensemble_expand", out, N, H, W, C, x.dtype, x)
+    if x.dtype == torch.float32:
+        rc = _lib.get().dasr_ensemble_expand_f32(_p(x), _p(a), _p(t), N, H, W, C, _lib.stream())
+    else:
+        rc = _lib.get().dasr_ensemble_expand_u8(_pu8(x), _pu8(a), _pu8(t), N, H, W, C, _lib.stream())
+    _batch_check("dasr_ensemble_expand", rc)
+    return a, t
+
+
+def ensemble_ingest_u8(frames, swap_rb=True, out=None):
+    """uint8 ``[N,H,W,C]`` camera frames -> the eight float32 members ``(a, t)``: ``ensemble_expand(frame_ingest_u8(frames,
+    swap_rb))`` bit for bit, in one pass (dasr_ensemble_ingest_u8)."""
+    if frames.dtype != torch.uint8 or frames.dim() != 4:
+        raise TypeError("dasr_amd: frames must be uint8 [N,H,W,C], got %s %s" % (frames.dtype, tuple(frames.shape)))
+    N, H, W, C = frames.shape
+    a, t = _ensemble_outs("ensemble_ingest_u8", out, N, H, W, C, torch.float32, frames)
+    rc = _lib.get().dasr_ensemble_ingest_u8(_pu8(frames), _p(a), _p(t), N, H, W, C, int(bool(swap_rb)), _lib.stream())
+    _batch_check("dasr_ensemble_ingest_u8", rc)
+    return a, t
+
+
+def ensemble_merge(y_a, y_t, lo, hi, out=None):
+    """``y_a [4N,H,W,C]``, ``y_t [4N,W,H,C]`` float32 (the members' results before the output clamp) -> ``[N,H,W,C]``:
+    every member mapped back and clamped to ``[lo, hi]`` (NaN kept), summed in member order, times 0.125
+    (dasr_ensemble_merge)."""
+    if y_a.dim() != 4 or y_t.dim() != 4 or y_a.shape[0] % 4 or \
+            tuple(y_t.shape) != (y_a.shape[0], y_a.shape[2], y_a.shape[1], y_a.shape[3]):
+        raise ValueError("dasr_amd: ensemble_merge takes [4N,H,W,C] and [4N,W,H,C], got %s and %s"
+                         % (tuple(y_a.shape), tuple(y_t.shape)))
+    N, H, W, C = y_a.shape[0] // 4, y_a.shape[1], y_a.shape[2], y_a.shape[3]
+    out = _batch_out(out, (N, H, W, C), torch.float32, y_a)
+    rc = _lib.get().dasr_ensemble_merge(_p(y_a), _p(y_t), _p(out), N, H, W, C, float(lo), float(hi), _lib.stream())
+    _batch_check("dasr_ensemble_merge", rc)
+    return out

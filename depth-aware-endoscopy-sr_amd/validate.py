@@ -66,6 +66,70 @@ def test(net, lq, depth, masks):
             net.train()
 
 
+def _expand_conditioning(depth, masks):
+    """The depth map ``[B,1,h,w]`` and the mask planes ``[B,K,h,w]`` under the eight symmetries of ``test_x8``:
+    ``((depth_a, masks_a), (depth_t, masks_t))``, group A ``[4B,.,h,w]`` and group T ``[4B,.,w,h]``.  A plane is an
+    ``[h,w,1]`` image to ``ops.ensemble_expand``, so each member block is again ``[B,K,..]``.  The masks' stamp travels:
+    attached region bytes are expanded with them (uint8), a soft stamp is repeated, unstamped masks stay unstamped."""
+    from . import graph, ops, prep
+    B, K, h, w = masks.shape
+    da, dt = ops.ensemble_expand(depth.contiguous().view(B, h, w, 1))
+    ma, mt = ops.ensemble_expand(masks.contiguous().view(B * K, h, w, 1))
+    ma, mt = ma.view(4 * B, K, h, w), mt.view(4 * B, K, w, h)
+    region = graph.attached_region(masks)
+    if region is not None:
+        ra, rt = ops.ensemble_expand(region.contiguous().view(B, h, w, 1))
+        for planes, r in ((ma, ra.view(4 * B, h, w)), (mt, rt.view(4 * B, w, h))):
+            planes._dasr_region = r
+            planes._dasr_version = ops.tensor_version(planes)
+    elif prep.marked_soft(masks):
+        prep.mark_soft(ma)
+        prep.mark_soft(mt)
+    return (da.view(4 * B, 1, h, w), ma), (dt.view(4 * B, 1, w, h), mt)
+
+
+@torch.no_grad()
+def test_x8(net, lq, depth, masks):
+    """Geometric self-ensemble inference, the depth-conditioned form of ``F_Model_depthCond.test_x8``
+    (F_model_depthCond.py:236-270): the frame under the eight flip / transpose symmetries - member ``m = v + 2h + 4t`` in the
+    reference's list order, ``v`` a flip along W, ``h`` along H, ``t`` a transpose applied last - through the generator,
+    each result mapped back, the eight averaged.  Arguments and result as ``test``: ``lq`` ``[B,3,h,w]``, ``depth``
+    ``[B,1,h,w]``, ``masks`` ``[B,K,h,w]`` float32 -> ``[B,3,sh,sw]`` float32 in ``[net.min, net.max]``; eval-mode forward
+    without autograd, the module's mode restored afterwards.
+
+    The reference's own ``test_x8`` calls ``self.netG(aug)`` with the image alone: it omits the depth map and the masks
+    and cannot run on ``DepthNet``, whose forward takes ``(input, depthMap, depthMask)``.  Here the depth map and the masks
+    (with their region bytes or soft stamp) are transformed with the image; member order and merge rule are the
+    reference's, and each member gets ``DepthNet.forward``'s output clamp before the mean.
+
+    Two forwards, always (also for square frames): members 0..3 (``h x w``) as one batch of 4B, members 4..7 (``w x h``)
+    as another.  Members of one group share a forward batch, and the fp16x2 split convolutions scale by a batch-wide
+    maximum, so the result is that of these two batched forwards, not of eight separate ones.  The flips and the merge are
+    HIP kernels on NHWC tensors (``ops.ensemble_expand`` / ``ops.ensemble_merge``); the sum is
+    ``0.125 * (((((((z0 + z1) + z2) + z3) + z4) + z5) + z6) + z7)`` in fp32."""
+    from . import ops
+    from .depthnet import _device_guard
+    for t, nm in ((lq, "lq"), (depth, "depth"), (masks, "masks")):
+        if t.dtype != torch.float32 or t.dim() != 4 or t.device != lq.device:
+            raise ValueError("test_x8: %s must be a 4-D float32 tensor on lq's device" % nm)
+    B, _, h, w = lq.shape
+    if tuple(depth.shape) != (B, 1, h, w) or masks.shape[0] != B or tuple(masks.shape[2:]) != (h, w):
+        raise ValueError("test_x8: lq %s, depth %s and masks %s do not belong together"
+                         % (tuple(lq.shape), tuple(depth.shape), tuple(masks.shape)))
+    was_training = net.training
+    net.eval()
+    try:
+        with _device_guard(lq):
+            xa, xt = ops.ensemble_expand(ops.nchw_to_nhwc(lq.contiguous()))
+            (da, ma), (dt, mt) = _expand_conditioning(depth, masks)
+            ya = net.infer_nhwc(xa, da, ma)
+            yt = net.infer_nhwc(xt, dt, mt)
+            return ops.nhwc_to_nchw(ops.ensemble_merge(ya, yt, net.min, net.max))
+    finally:
+        if was_training:
+            net.train()
+
+
 def validate(net, frames, scale):
     """The validation loop of codes/train.py:219-262 over an iterable of `(LQ, GT, Depth, DepthMaskList)` frames
     (`[1,3,h,w]`, `[1,3,sh,sw]`, `[1,1,h,w]`, `[1,K,h,w]`): SSIM of the [0,1] tensors (pytorch_ssim), PSNR of the
@@ -83,7 +147,8 @@ def validate(net, frames, scale):
     return psnr_sum / max(n, 1), ssim_sum / max(n, 1), n
 
 
-def validate_u8(net, frames, scale, num_masks=10, fixed_range=False, use_graph=False, soft_masks=None):
+def validate_u8(net, frames, scale, num_masks=10, fixed_range=False, use_graph=False, soft_masks=None,
+                self_ensemble=False):
     """The loop of ``validate()`` for a video source: ``frames`` yields ``(LQ, GT, Depth)`` with ``LQ`` a ``uint8``
     ``[1,h,w,3]`` (or ``[h,w,3]``) BGR frame as ``cv2`` reads it, ``GT`` the ``[1,3,sh,sw]`` float tensor and ``Depth``
     ``[1,1,h,w]``; a fourth item (the reference loader's mask list) is ignored, the masks are binned on the device.
@@ -92,11 +157,12 @@ def validate_u8(net, frames, scale, num_masks=10, fixed_range=False, use_graph=F
     ``scale``-pixel border cropped (``dasr_frame_ssd_u8``; ``inf`` at ``ssd == 0``); SSIM is ``dasr_ssim`` of the [0,1]
     tensors as in ``validate()``.  Nothing is read back per frame: the sums stay on the device and come to the host in
     one transfer at the end.  ``soft_masks``: ``FrameUpscaler``'s (None: one-hot masks; a number: soft masks of that blend
-    width).  Returns (avg_psnr, avg_ssim, n)."""
+    width).  ``self_ensemble``: ``FrameUpscaler``'s - SR is then ``test_x8``'s geometric self-ensemble, the figures of a
+    paper's "+" rows.  Returns (avg_psnr, avg_ssim, n)."""
     from . import ops
     from .video import FrameUpscaler
     up = FrameUpscaler(net, num_masks=num_masks, fixed_range=fixed_range, use_graph=use_graph, min_max=(0, 1),
-                       soft_masks=soft_masks)
+                       soft_masks=soft_masks, self_ensemble=self_ensemble)
     dev = up.device
     CHUNK = 256
     chunks, counts = [], []              # int64 [2*CHUNK] each: ssd in the first half, ssim (float32 bits) in the second

@@ -22,12 +22,20 @@ from .depthnet import _device_guard
 class _Slot:
     """Static buffers of one frame in flight: inputs and outputs of the (captured) chain, and their pinned host twins."""
 
-    def __init__(self, B, h, w, C, scale, device):
+    def __init__(self, B, h, w, C, scale, device, ensemble=False):
         self.frames = torch.empty((B, h, w, C), dtype=torch.uint8, device=device)
         self.depth = torch.empty((B, 1, h, w), dtype=torch.float32, device=device)
-        self.x = torch.empty((B, h, w, C), dtype=torch.float32, device=device)
         self.out = torch.empty((B, scale * h, scale * w, C), dtype=torch.uint8, device=device)
         self.y = None                    # conv_output's NHWC result of the last run (before the clamp), for validate_u8
+        if ensemble:
+            # self-ensemble: the eight members of the image and of the depth map, group A (h x w) and group T (w x h) as
+            # batches of 4B, and the merged (already clamped) result
+            f32 = dict(dtype=torch.float32, device=device)
+            self.xa, self.xt = torch.empty((4 * B, h, w, C), **f32), torch.empty((4 * B, w, h, C), **f32)
+            self.da, self.dt = torch.empty((4 * B, 1, h, w), **f32), torch.empty((4 * B, 1, w, h), **f32)
+            self.y = torch.empty((B, scale * h, scale * w, C), **f32)
+        else:
+            self.x = torch.empty((B, h, w, C), dtype=torch.float32, device=device)
         self.graph = None
         self.sig = None
         if device.type == "cuda":
@@ -40,8 +48,8 @@ class _Slot:
 
 
 class _ShapeState:
-    def __init__(self, B, h, w, C, scale, device):
-        self.args = (B, h, w, C, scale, device)
+    def __init__(self, *args):
+        self.args = args                 # _Slot's: (B, h, w, C, scale, device, ensemble)
         self.slots = [_Slot(*self.args)]
         self.eager_calls = 0
 
@@ -69,6 +77,14 @@ class FrameUpscaler:
     is then what ``validate.test`` gives with ``prep.depth_to_soft_masks(depth, num_masks, fixed_range, width)``.  It is a
     constructor constant (not part of a captured graph's signature).
 
+    ``self_ensemble=True``: geometric self-ensemble, ``validate.test_x8`` per frame - the result is, byte for byte,
+    ``tensor2img(validate.test_x8(net, img2tensor(frames), depth, masks)[b])``.  The chain ingests the frame into its eight
+    flip / transpose members (``dasr_ensemble_ingest_u8``), expands the depth map, bins the masks from the expanded depth
+    maps (binning is pointwise given a sample's minimum and maximum, which do not depend on pixel order), runs two
+    forwards of batch 4B - ``h x w`` and ``w x h`` - and merges (``dasr_ensemble_merge``) before the emit.  Roughly
+    eight times the work per frame; a constructor constant like ``soft_masks``; everything below holds for it unchanged, the
+    captured graph then contains both forwards.
+
     ``use_graph=True`` (GPU only, ignored elsewhere): the first two calls of an input shape run eagerly - the fold cache,
     the allocator's pools and the side stream of the depth branch come into being - the third captures
     ingest -> masks -> forward -> emit into one graph over static buffers and replays it, later calls copy in, replay and
@@ -77,8 +93,10 @@ class FrameUpscaler:
     compares per kernel), and on a mismatch the graph is dropped and the shape starts its warm-up again.  One graph per
     input shape (two when ``upscale_iter`` is used), for the ``max_shapes`` most recently used shapes."""
 
-    def __init__(self, net, num_masks=10, fixed_range=False, use_graph=True, min_max=(0, 1), max_shapes=4, soft_masks=None):
+    def __init__(self, net, num_masks=10, fixed_range=False, use_graph=True, min_max=(0, 1), max_shapes=4, soft_masks=None,
+                 self_ensemble=False):
         self.net = net
+        self.self_ensemble = bool(self_ensemble)
         self.num_masks = int(num_masks)
         self.fixed_range = bool(fixed_range)
         self.soft_masks = None if soft_masks is None else float(soft_masks)
@@ -105,7 +123,7 @@ class FrameUpscaler:
                 if self.device.type == "cuda":
                     torch.cuda.synchronize(self.device)
                 self._shapes.popitem(last=False)
-            st = self._shapes[key] = _ShapeState(B, h, w, C, self.net.scale, self.device)
+            st = self._shapes[key] = _ShapeState(B, h, w, C, self.net.scale, self.device, self.self_ensemble)
         else:
             self._shapes.move_to_end(key)
         return st
@@ -117,16 +135,27 @@ class FrameUpscaler:
                 tuple((p.data_ptr(), ops.tensor_version(p)) for p in self.net._resolve_params()))
 
     # ---- the chain -----------------------------------------------------------------------------------------------------
-    def _chain(self, slot):
-        ops.frame_ingest_u8(slot.frames, swap_rb=True, out=slot.x)
+    def _masks(self, depth):
         if self.soft_masks is not None:
-            planes = ops.depth_to_masks_soft(slot.depth, self.num_masks, self.soft_masks, self.fixed_range)
+            planes = ops.depth_to_masks_soft(depth, self.num_masks, self.soft_masks, self.fixed_range)
             prep.mark_soft(planes)                       # as prep.depth_to_soft_masks: the general kernels, no read-back
         else:
-            planes, region = ops.depth_to_masks(slot.depth, self.num_masks, self._edges, want_planes=True)
+            planes, region = ops.depth_to_masks(depth, self.num_masks, self._edges, want_planes=True)
             planes._dasr_region = region                 # as prep.depth_to_masks: no compression pass, no flag read-back
             planes._dasr_version = ops.tensor_version(planes)
-        slot.y = self.net.infer_nhwc(slot.x, slot.depth, planes)
+        return planes
+
+    def _chain(self, slot):
+        if self.self_ensemble:
+            B, _, h, w = slot.depth.shape
+            ops.ensemble_ingest_u8(slot.frames, swap_rb=True, out=(slot.xa, slot.xt))
+            ops.ensemble_expand(slot.depth.view(B, h, w, 1), out=(slot.da.view(4 * B, h, w, 1), slot.dt.view(4 * B, w, h, 1)))
+            y_a = self.net.infer_nhwc(slot.xa, slot.da, self._masks(slot.da))
+            y_t = self.net.infer_nhwc(slot.xt, slot.dt, self._masks(slot.dt))
+            ops.ensemble_merge(y_a, y_t, self.net.min, self.net.max, out=slot.y)
+        else:
+            ops.frame_ingest_u8(slot.frames, swap_rb=True, out=slot.x)
+            slot.y = self.net.infer_nhwc(slot.x, slot.depth, self._masks(slot.depth))
         ops.frame_emit_u8(slot.y, self.net.min, self.net.max, self.min_max, swap_rb=True, out=slot.out)
 
     def _compute(self, st, slot):
@@ -200,8 +229,8 @@ class FrameUpscaler:
     def upscale_device(self, frames, depth):
         """``upscale`` without the download and without any wait: returns ``(sr_u8, y)`` ON THE DEVICE - ``sr_u8``
         ``[B,s*h,s*w,3]`` uint8 BGR and ``y`` ``[B,s*h,s*w,3]`` float32, conv_output's NHWC result before the clamp to
-        ``[net.min, net.max]`` - as work queued on the current stream.  Both are this upscaler's static buffers: they are
-        valid until the next ``upscale`` / ``upscale_device`` call with frames of the same shape (which overwrites them,
+        ``[net.min, net.max]`` (with ``self_ensemble`` the merged result, already clamped) - as work queued on the current
+        stream.  Both are this upscaler's static buffers: they are valid until the next ``upscale`` / ``upscale_device`` call with frames of the same shape (which overwrites them,
         in stream order) and must be consumed on the same stream, or after a synchronise, before that.  The call never
         blocks on the GPU except to make sure the previous frame has left the pinned staging buffers.  For consumers that
         keep working on the device (``validate.validate_u8``)."""

@@ -611,6 +611,33 @@ int dasr_batch_plane_f32(const float* in, float* out, const int* origins, const 
 int dasr_batch_plane_u8(const unsigned char* in, unsigned char* out, const int* origins, const unsigned char* flags, int B,
                         int C, int h, int w, int ch, int cw, int allow_transpose, void* stream);
 
+/* ---- geometric self-ensemble inference (csrc/ensemble.hip) ------------------------------------------------------------
+ * The reference's test_x8 (F_model_depthCond.py:236-270): the frame under the eight flip / transpose symmetries, each
+ * result mapped back, the eight averaged.  Member m = v + 2 h + 4 t in the reference's list order: v flips along W (its
+ * 'v', [:, :, :, ::-1]), h along H, t transposes last.  Members 0..3 are group A, images of H x W; members 4..7 group T,
+ * images of W x H; member m of image n is image (m % 4) * N + n of its group's tensor.  With fh(r) = h ? H-1-r : r and
+ * fv(c) = v ? W-1-c : c:   t = 0: x_m[n,r,c,:] = x[n,fh(r),fv(c),:]     t = 1: x_m[n,r,c,:] = x[n,fh(c),fv(r),:].
+ * C must be 1 or 3 (DASR_E_UNSUPPORTED otherwise); N <= 65535.  No workspace, no atomics.
+ *
+ * dasr_ensemble_expand_f32 / _u8 (the `_transform` of F_model_depthCond.py:236-270 for all eight members): src [N,H,W,C]
+ * -> out_a [4N,H,W,C], out_t [4N,W,H,C], a bit-exact move.  With C = 1 they take the depth map, the K mask planes
+ * ([B,K,h,w] as N = B*K images: each member block is again [B,K,..]) and the region bytes (u8). */
+int dasr_ensemble_expand_f32(const float* src, float* out_a, float* out_t, int N, int H, int W, int C, void* stream);
+int dasr_ensemble_expand_u8(const unsigned char* src, unsigned char* out_a, unsigned char* out_t, int N, int H, int W,
+                            int C, void* stream);
+/* dasr_ensemble_ingest_u8 (F_model_depthCond.py:236-270 applied to a camera frame): dasr_frame_ingest_u8 followed by
+ * dasr_ensemble_expand_f32 in one pass, bit for bit: every value is (float)byte / 255.0f (IEEE division); swap_rb != 0
+ * with C == 3 reverses the channel order. */
+int dasr_ensemble_ingest_u8(const unsigned char* frames, float* out_a, float* out_t, int N, int H, int W, int C,
+                            int swap_rb, void* stream);
+/* dasr_ensemble_merge (the inverse transforms and the mean of F_model_depthCond.py:236-270: i > 3 transpose, i % 4 > 1 h,
+ * i % 2 == 1 v) with the output clamp of DepthNet.forward (sftmd_arch.py:950) applied to every member first: y_a
+ * [4N,H,W,C], y_t [4N,W,H,C] are conv_output's results before the clamp;
+ *   z_m[n,r,c,:] = clamp(y_m[n,fh(r),fv(c),:]) (t = 0),   clamp(y_m[n,fv(c),fh(r),:]) (t = 1),   clamp keeps NaN
+ *   out[n,r,c,:] = 0.125f * (((((((z0 + z1) + z2) + z3) + z4) + z5) + z6) + z7), every addition rounded on its own. */
+int dasr_ensemble_merge(const float* y_a, const float* y_t, float* out, int N, int H, int W, int C, float lo, float hi,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

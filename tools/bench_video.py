@@ -9,6 +9,9 @@
 for one configuration (--config x8: the x8 net on a 128x160 frame; x2: the x2 net on a 540x960 frame; --dtype fp32|bf16;
 --soft-masks WIDTH: soft depth masks of that blend width in every arm, default one-hot; its entry's key ends in _softWIDTH).
 tools/bench_soft_prep.py compares the two mask kinds in one process, alternating.
+--self-ensemble: arms b, c and d run a second time with FrameUpscaler(self_ensemble=True) (validate.test_x8 per frame: eight
+flip / transpose members, two forwards of batch 4) as arms b_x8ens, c_x8ens, d_x8ens, alternating with the plain arms in the
+same process, and the entry - plain arms, ensemble arms and the ratio of their medians - goes under a key that ends in _x8ens.
 Every arm gets --warmup frames, then --rounds rounds of --frames frames; the arms alternate within a round.  Each timed
 call ends in a device synchronise (a: the download; b, c: the stream synchronise of upscale; d: the download event of the
 frame handed out).  Median and p95 over all timed frames of an arm, and the median of each round, go into one entry of
@@ -44,6 +47,8 @@ def main():
     ap.add_argument("--arms", default="abcd")
     ap.add_argument("--soft-masks", type=float, default=None, metavar="WIDTH",
                     help="soft depth masks of this blend width (prep.depth_to_soft_masks) in every arm; default: one-hot")
+    ap.add_argument("--self-ensemble", action="store_true",
+                    help="also time arms b, c, d with FrameUpscaler(self_ensemble=True); the entry's key ends in _x8ens")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     sys.path.insert(0, a.root)
@@ -90,20 +95,33 @@ def main():
             return ms
         return run
 
-    def run_d(n):
-        # n + 2 frames in, the first two intervals (the pipeline filling) dropped: n steady-state intervals
-        ms, t0 = [], time.perf_counter()
-        for _ in up_d.upscale_iter(pool[i % len(pool)] for i in range(n + 2)):
-            t1 = time.perf_counter()
-            ms.append((t1 - t0) * 1e3)
-            t0 = t1
-        return ms[2:]
+    def pipelined(up):
+        def run(n):
+            # n + 2 frames in, the first two intervals (the pipeline filling) dropped: n steady-state intervals
+            ms, t0 = [], time.perf_counter()
+            for _ in up.upscale_iter(pool[i % len(pool)] for i in range(n + 2)):
+                t1 = time.perf_counter()
+                ms.append((t1 - t0) * 1e3)
+                t0 = t1
+            return ms[2:]
+        return run
 
-    arms = {"a": per_call(arm_a), "b": per_call(up_b.upscale), "c": per_call(up_c.upscale), "d": run_d}
+    arms = {"a": per_call(arm_a), "b": per_call(up_b.upscale), "c": per_call(up_c.upscale), "d": pipelined(up_d)}
     arms = {k: v for k, v in arms.items() if k in a.arms}
     f0, d0 = pool[0]
     ref = up_b.upscale(f0, d0)
     same = {k: bool(np.array_equal(fn(f0, d0), ref)) for k, fn in (("a", arm_a), ("c", up_c.upscale)) if k in arms}
+    ens = {}
+    if a.self_ensemble:
+        ens = {k: FrameUpscaler(net, num_masks=K, use_graph=k != "b", soft_masks=soft, self_ensemble=True)
+               for k in "bcd" if k in a.arms}
+        for k, up in ens.items():
+            arms[k + "_x8ens"] = pipelined(up) if k == "d" else per_call(up.upscale)
+        if "b" in ens:
+            ref8 = ens["b"].upscale(f0, d0)
+            same["b_x8ens_differs_from_b"] = bool(not np.array_equal(ref8, ref))
+            if "c" in ens:
+                same["c_x8ens"] = bool(np.array_equal(ens["c"].upscale(f0, d0), ref8))       # (equal to b_x8ens)
     for run in arms.values():
         run(a.warmup)
     torch.cuda.synchronize()
@@ -115,16 +133,22 @@ def main():
             allms[k] += ms
             rounds[k].append(stats(ms)["median_ms"])
     entry = dict(config=a.config, dtype=a.dtype, soft_masks=soft, scale=scale, lr_hw=[h, w], frames=a.frames, rounds=a.rounds,
-                 warmup=a.warmup, outputs_equal_to_b=same, graph_replays=dict(c=up_c.replays, d=up_d.replays),
+                 warmup=a.warmup, outputs_equal_to_b=same,
+                 graph_replays=dict(dict(c=up_c.replays, d=up_d.replays),
+                                    **{k + "_x8ens": up.replays for k, up in ens.items() if k != "b"}),
                  arms={k: dict(stats(v), round_medians_ms=rounds[k]) for k, v in allms.items()},
                  device=torch.cuda.get_device_name(0), peak_mem_gb=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2))
+    if ens:
+        med = {k: v["median_ms"] for k, v in entry["arms"].items()}
+        entry["self_ensemble"] = True
+        entry["x8ens_over_plain"] = {k: round(med[k + "_x8ens"] / med[k], 2) for k in ens if k in med}
     print(json.dumps(entry), flush=True)
     if a.out:
         data = {}
         if os.path.exists(a.out):
             with open(a.out) as fh:
                 data = json.load(fh)
-        data["%s_%s%s" % (a.config, a.dtype, "" if soft is None else "_soft%g" % soft)] = entry
+        data["%s_%s%s" % (a.config, a.dtype, ("" if soft is None else "_soft%g" % soft) + ("_x8ens" if ens else ""))] = entry
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as fh:
             json.dump(data, fh, indent=1, sort_keys=True)
