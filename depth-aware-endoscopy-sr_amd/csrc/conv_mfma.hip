@@ -415,6 +415,13 @@ static int cm_tile_rows(int B, int H, int W, int Cout) {
     return ((H % 16) == 0 && (wg16 % 256 == 0 || wg16 >= 2048)) ? 16 : 8;
 }
 
+// read-only: the tile rows (8 or 16) launch_conv_mfma picks for this forward geometry, 0 where this family does not run it
+extern "C" int dasr_conv2d_fwd_tile_rows(int B, int H, int W, int Cin, int Cout) {
+    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return 0;
+    ConvGeom g{B, H, W, Cin, H, W, Cout, 3, 3, 1, 1, 0};
+    return conv_mfma_supported(g) ? cm_tile_rows(B, H, W, Cout) : 0;
+}
+
 template <int WMODE>
 static int launch_conv_mfma(ConvMfmaArgs& a, void* stream) {
     // 16-row tiles (one 512-thread workgroup per CU) stage every weight slice once for twice the pixels; 8-row

@@ -393,6 +393,11 @@ def conv2d_fwd(x, w, bias=None, residual=None, stride=1, pad=1, transposed=False
     return y
 
 
+def conv2d_fwd_tile_rows(B, H, W, Cin, Cout):
+    """Tile rows (8 or 16) of the fp32 MFMA kernel that carries this 3x3 / stride 1 / pad 1 geometry, 0: another family."""
+    return int(_lib.get().dasr_conv2d_fwd_tile_rows(B, H, W, Cin, Cout))
+
+
 def conv2d_epilogue_bwd(dy, y, Ho, Wo, Cout, act, ps_r, amax=None):
     B = y.shape[0]
     dconv = empty((B, Ho, Wo, Cout), y, y.dtype)

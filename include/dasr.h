@@ -113,6 +113,10 @@ int dasr_weight_pack_bwd(const float* dw_hwio, const float* v, const float* g, c
 int dasr_conv2d_fwd(const float* x, const float* w_hwio, const float* bias, const float* residual, float* y, float* y_amax,
                     int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad,
                     int transposed, int act, int ps_r, void* stream);
+/* Read-only query for tests: the pixel-tile rows of the MFMA kernel that dasr_conv2d_fwd / dasr_conv2d_fwd_stats run for a
+ * 3x3 / stride 1 / pad 1 convolution of this geometry - 8 (256-thread workgroups) or 16 (512-thread workgroups) - and 0
+ * where another kernel family carries it.  The data gradient of a Cin -> Cout layer runs the form of (Cout, Cin). */
+int dasr_conv2d_fwd_tile_rows(int B, int H, int W, int Cin, int Cout);
 /* dasr_conv2d_fwd for a 3x3 / stride 1 / pad 1 convolution with bias and no activation, PLUS the statistics
  * nn.InstanceNorm2d(affine=False) needs of its output (sftmd_arch.py:811-820: `conv1 = Sequential(Conv2d, InstanceNorm2d)`):
  * mean[b,c], var[b,c] (biased) over the H*W pixels, as dasr_instnorm_stats(y) returns them.  On the MFMA path the

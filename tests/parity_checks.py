@@ -147,9 +147,12 @@ def check_conv_variants(device, seed=0):
         (8, 32, 3, 1, 1, False, 1, 1, False, 7, 9),
         (64, 64, 3, 1, 1, False, 2, 1, False, 16, 33), (32, 32, 3, 1, 1, False, 1, 1, True, 32, 20),
         (16, 128, 3, 1, 1, False, 2, 2, False, 16, 40),
-        # full-width tiles (fast epilogue), 16-row tiles, several N slices, a tile count that is not a multiple of 8
-        # (padded workgroups of the XCD-aware order), residual / PixelShuffle through the fast epilogue, the 32x128
-        # and 64x32 wgrad blocks
+        # full-width tiles (fast epilogue), several N slices, a tile count that is not a multiple of 8 (padded
+        # workgroups of the XCD-aware order), residual / PixelShuffle through the fast epilogue, the 32x128 and 64x32
+        # wgrad blocks.  All of these run the 8-ROW form of k_conv3x3_mfma: H % 16 == 0 is not enough for the 16-row
+        # one, its grid must also be a multiple of 256 workgroups (cm_tile_rows, csrc/conv_mfma.hip).  The 16-row
+        # forms run in tests/fp32_exact_checks.py: check_int_conv3_16row, check_int_dgrad_act, check_int_fwd_stats,
+        # check_mantissa_fwd_dgrad, check_bound_16row_nt1 / _nt2, each asserting the form from ops.conv2d_fwd_tile_rows
         (128, 128, 3, 1, 1, False, 0, 1, False, 16, 32, 3), (64, 256, 3, 1, 1, False, 2, 2, False, 32, 64, 1),
         (32, 64, 3, 1, 1, False, 1, 1, False, 48, 32, 2), (64, 64, 3, 1, 1, False, 0, 1, True, 16, 64, 2),
         (64, 32, 3, 1, 1, False, 2, 1, False, 16, 32, 2), (32, 128, 3, 1, 1, False, 2, 2, False, 16, 32, 2),
@@ -402,19 +405,39 @@ def check_fused_loss(device):
 
 
 def check_dgrad_act(device):
-    """dasr_conv2d_dgrad_act == dgrad, times act'(x), through the inverse PixelShuffle map (3x3 MFMA and 9x9 paths)."""
+    """dasr_conv2d_dgrad_act == dgrad, times act'(x), through the inverse PixelShuffle map (3x3 MFMA and 9x9 paths), on
+    Gaussian data.  The reference is float64 torch (the transposed convolution written out), held per element to the
+    any-order fp32 summation bound gamma_n * conv(|dconv|, |w|) * act'(x), n = K K Cout + 3, plus the one rounding of the
+    multiply by act' (tests/fp32_exact_checks.py, C, has the derivation; check_int_dgrad_act there is the exact form of
+    this check, 16-row tiles included).  Second, as before: the library's own dgrad times act'(x) within 1e-6."""
     gen = torch.Generator().manual_seed(5)
+    u = 2.0 ** -24
     for (cin, cout, k, pad, H, W, r, act) in [(32, 64, 3, 1, 8, 34, 1, ops.ACT_RELU), (32, 32, 3, 1, 16, 36, 2, ops.ACT_LRELU),
                                               (64, 32, 3, 1, 6, 33, 3, ops.ACT_LRELU), (32, 3, 9, 4, 10, 66, 2, ops.ACT_LRELU),
                                               (32, 3, 9, 4, 12, 30, 1, ops.ACT_RELU)]:
         B = 2
-        x_act = torch.randn(B, H, W, cin, generator=gen).to(device)
-        w = ops.pack_hwio((torch.randn(k, k, cin, cout, generator=gen) * 0.1).to(device))
-        dconv = torch.randn(B, H, W, cout, generator=gen).to(device)
+        x_cpu = torch.randn(B, H, W, cin, generator=gen)
+        w_cpu = torch.randn(k, k, cin, cout, generator=gen) * 0.1
+        d_cpu = torch.randn(B, H, W, cout, generator=gen)
+        x_act, w, dconv = x_cpu.to(device), ops.pack_hwio(w_cpu.to(device)), d_cpu.to(device)
         assert ops.conv2d_dgrad_act_supported(x_act.shape, w, dconv.shape, 1, pad, False, r)
         got = ops.conv2d_dgrad_act(dconv, w, x_act, act, r, 1, pad, False)
-        ref = ops.conv2d_dgrad(dconv, w, x_act.shape, 1, pad, False)
         slope = 0.0 if act == ops.ACT_RELU else 0.2
+        # ---- float64, from scratch
+        d64, w64 = nchw(d_cpu).double(), w_cpu.permute(3, 2, 0, 1).double()
+        g64 = torch.where(nchw(x_cpu) > 0, torch.ones((), dtype=torch.float64),
+                          torch.tensor(slope, dtype=torch.float32).double())
+        ref64 = F.conv_transpose2d(d64, w64, None, stride=1, padding=pad) * g64
+        n = k * k * cout + 3
+        bound = n * u / (1 - n * u) * F.conv_transpose2d(d64.abs(), w64.abs(), None, stride=1, padding=pad) * g64 + \
+            u * ref64.abs()
+        if r > 1:
+            ref64, bound = F.pixel_unshuffle(ref64, r), F.pixel_unshuffle(bound, r)
+        err = (nchw(got.cpu()).double() - ref64).abs()
+        assert got.shape == nhwc(ref64).shape
+        assert bool((err <= bound).all()), (cin, cout, k, r, "error / bound", float((err / bound.clamp_min(1e-300)).max()))
+        # ---- the library's own dgrad
+        ref = ops.conv2d_dgrad(dconv, w, x_act.shape, 1, pad, False)
         ref = ref * torch.where(x_act > 0, torch.ones_like(x_act), torch.full_like(x_act, slope))
         ref = nhwc(F.pixel_unshuffle(nchw(ref.cpu()), r)) if r > 1 else ref.cpu()
         assert got.shape == ref.shape
@@ -848,8 +871,10 @@ def check_large_frame_x2(device, H=1080, W=1920):
 
 def check_conv_fwd_stats(device):
     """dasr_conv2d_fwd_stats: the convolution output is bit-identical to dasr_conv2d_fwd and the statistics match
-    dasr_instnorm_stats of that output (and torch's biased variance), on the fused path (W % 32 == 0: 8- and 16-row
-    tiles, ragged last tile row, 32 / 64 / 128 channels) and on the fallback (W % 32 != 0, Cin not a multiple of 16)."""
+    dasr_instnorm_stats of that output (and torch's biased variance), on the fused path (W % 32 == 0: 8-row tiles - none
+    of these shapes reaches the 16-row form, whose statistics epilogue and workspace check_int_fwd_stats of
+    tests/fp32_exact_checks.py run -, ragged last tile row, 32 / 64 / 128 channels) and on the fallback (W % 32 != 0, Cin
+    not a multiple of 16)."""
     worst = 0.0
     for (B, H, W, Cin, Cout) in ((2, 16, 32, 64, 64), (1, 21, 64, 64, 64), (2, 40, 32, 32, 32), (1, 32, 96, 128, 128),
                                  (2, 9, 20, 64, 64), (1, 16, 32, 8, 32)):
