@@ -615,8 +615,14 @@ __global__ void __launch_bounds__(256, HAS_RES ? DASR_SEAN_RES_OCC : 3) k_sean_f
                     o.x = o.x <= 0.f ? 0.f : o.x; o.y = o.y <= 0.f ? 0.f : o.y;     // NaN stays NaN, as in F.relu
                     o.z = o.z <= 0.f ? 0.f : o.z; o.w = o.w <= 0.f ? 0.f : o.w;
                 }
-                if (AMAX) om = dasr_amax4(om, o);     // (clamped / shadow lanes hold duplicates of stored values)
                 if (live && y < g.H && x < g.W) {
+                    // Only what is stored counts for max |out|.  (The maximum used to be taken over every lane, on the
+                    // belief that clamped and shadow lanes hold duplicates of stored values.  They do not: a clamped lane
+                    // reads t / gb2 of the image's last row or column but gathers gamma1 / beta1 at its own position
+                    // beyond it, and a dead lane of the last 64-slice pairs channels 0..3 with zero rows of D, so the
+                    // fused maximum could exceed max |out| - tests/sean_exact_checks.py found 197.06 against 182.06 at
+                    // C = 64, K = 16, 2 x 9 x 33 on isolated masks, on the emulator and on the MI355X alike.)
+                    if (AMAX) om = dasr_amax4(om, o);
                     TA* dst = (TA*)(orow + ((unsigned)x * (unsigned)g.C + (unsigned)c) * (unsigned)sizeof(TA));
                     st4_nt(dst, o);       // written once, read by the next kernel from HBM: do not displace the inputs
                 }
