@@ -31,6 +31,7 @@ _CTYPES = {
     "const int*": ctypes.c_void_p, "int*": ctypes.c_void_p,
     "const unsigned short*": ctypes.c_void_p, "unsigned short*": ctypes.c_void_p,      # bf16 bits
     "unsigned long long*": ctypes.c_void_p, "double": ctypes.c_double,                  # video frames (csrc/frame.hip)
+    "double*": ctypes.c_void_p,                                                          # image metrics (csrc/metrics.hip)
     "const dasr_pack_job*": ctypes.c_void_p, "const dasr_split_job*": ctypes.c_void_p,  # job tables (structs below)
 }
 

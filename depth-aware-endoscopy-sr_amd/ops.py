@@ -987,6 +987,42 @@ def frame_ssd_u8(a, b, crop=0, out=None):
     return out
 
 
+# ---- the test script's metrics of uint8 images (csrc/metrics.hip) ------------------------------
+def image_metrics_u8(a, b, crop=0, out=None):
+    """The sums behind PSNR, SSIM, PSNR_Y and SSIM_Y of the reference's test script for two uint8 [B,H,W,C] batches (C = 3:
+    BGR; C = 1) inside a ``crop``-pixel border: ``(ssd int64 [B], sums float64 [B,3])`` on the device - the exact sum of
+    squared differences, the sum of squared luma differences, the sum of the float64 valid-window SSIM map over positions
+    and channels, and that of the luma image (dasr_image_metrics_u8; ``validate.image_metrics`` turns them into the four
+    figures).  ``out``: ``(ssd, sums)`` tensors to write into, e.g. slices of a caller's result buffers.  Refused with
+    ValueError: C other than 1 or 3, fewer than 11 rows or columns left inside the border."""
+    for t, nm in ((a, "a"), (b, "b")):
+        if not torch.is_tensor(t) or t.dtype != torch.uint8 or t.dim() != 4:
+            raise TypeError("dasr_amd: image_metrics_u8: %s must be a uint8 [B,H,W,C] tensor" % nm)
+    if a.shape != b.shape or a.device != b.device:
+        raise ValueError("dasr_amd: image_metrics_u8: a %s on %s and b %s on %s do not belong together"
+                         % (tuple(a.shape), a.device, tuple(b.shape), b.device))
+    B, H, W, C = a.shape
+    crop = int(crop)
+    if C not in (1, 3):
+        raise ValueError("dasr_amd: image_metrics_u8: C must be 1 or 3, got %d" % C)
+    if B < 1 or crop < 0 or H - 2 * crop < 11 or W - 2 * crop < 11:
+        raise ValueError("dasr_amd: image_metrics_u8: %dx%d frames with a border of %d leave less than the 11x11 window"
+                         % (H, W, crop))
+    if out is None:
+        ssd = torch.empty((B,), dtype=torch.int64, device=a.device)
+        sums = torch.empty((B, 3), dtype=torch.float64, device=a.device)
+    else:
+        ssd, sums = out
+        if ssd.dtype != torch.int64 or ssd.numel() != B or sums.dtype != torch.float64 or sums.numel() != 3 * B \
+                or ssd.device != a.device or sums.device != a.device:
+            raise ValueError("dasr_amd: image_metrics_u8: out must be (int64 [%d], float64 [%d,3]) on %s" % (B, B, a.device))
+    nbytes = int(_lib.get().dasr_image_metrics_u8_workspace(B, H, W, C, crop))
+    ws = torch.empty((max(nbytes, 8) // 8,), dtype=torch.int64, device=a.device)
+    _call("dasr_image_metrics_u8", _pu8(a), _pu8(b), _lib.ptr(ssd, dtype=torch.int64), _lib.ptr(sums, dtype=torch.float64),
+          _lib.ptr(ws, dtype=torch.int64), nbytes, B, H, W, C, crop)
+    return ssd, sums
+
+
 # ---- training batches from uint8 HR frames (csrc/batch.hip) --------------------------------------------------------
 def _pi32(t, allow_none=False):
     return _lib.ptr(t, allow_none, dtype=torch.int32)

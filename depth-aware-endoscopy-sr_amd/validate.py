@@ -198,3 +198,103 @@ def validate_u8(net, frames, scale, num_masks=10, fixed_range=False, use_graph=F
         psnr_sum += inf if ssd == 0 else 20 * math.log10(255.0 / math.sqrt(ssd / cnt))
         ssim_sum += float(buf[CHUNK:].view(torch.float32)[j])
     return psnr_sum / n, ssim_sum / n, n
+
+
+def _figures(ssd, sums, Hc, Wc, C):
+    """The test script's figures of one frame from dasr_image_metrics_u8's sums (include/dasr.h): psnr and ssim, and for a
+    3-channel image psnr_y and ssim_y (test.py:117-135 has no luma figures for a gray one)."""
+    inf = float("inf")
+    positions = (Hc - 10) * (Wc - 10)
+    out = dict(psnr=inf if ssd == 0 else 20 * math.log10(255.0 / math.sqrt(ssd / (Hc * Wc * C))),
+               ssim=sums[1] / (positions * C))
+    if C == 3:
+        out["psnr_y"] = inf if sums[0] == 0 else 20 * math.log10(255.0 / math.sqrt(sums[0] / (Hc * Wc)))
+        out["ssim_y"] = sums[2] / positions
+    return out
+
+
+def image_metrics(sr_u8, gt_u8, crop_border):
+    """PSNR, SSIM, PSNR_Y and SSIM_Y as the reference's test script computes them (codes/test.py:97-135) for uint8 images
+    ``[B,H,W,C]`` (or one ``[H,W,C]``), C = 3 in BGR order or C = 1, tensors where the library computes:
+    ``calculate_psnr`` and ``calculate_ssim`` (utils/util.py:646-697: the float64, valid-window, [0, 255]-scale "same as
+    MATLAB" SSIM) of the images with ``crop_border`` pixels cut off every side (0: none), and of their BT.601 luma
+    (``bgr2ycbcr(only_y=True)`` of the float image, data/util.py:199-213).  One kernel pass per call
+    (``ops.image_metrics_u8``) and one read-back; the logarithms and divisions happen on the host.  Returns a list with one
+    ``dict(psnr=, ssim=, psnr_y=, ssim_y=)`` of Python floats per frame (the dict itself for a single ``[H,W,C]`` image);
+    a gray image has no ``_y`` entries.  ``psnr`` is ``inf`` for identical images.  This SSIM is not ``validate.ssim``'s
+    number (``pytorch_ssim``: zero padding, fp32, [0, 1] tensors).  Fewer than 11 rows or columns inside the border raise
+    ValueError (the reference returns NaN there)."""
+    from . import ops
+    if not (torch.is_tensor(sr_u8) and torch.is_tensor(gt_u8)):
+        raise TypeError("image_metrics: sr_u8 and gt_u8 must be uint8 tensors")
+    single = sr_u8.dim() == 3 and gt_u8.dim() == 3
+    a, b = (sr_u8[None], gt_u8[None]) if single else (sr_u8, gt_u8)
+    crop = int(crop_border)
+    ssd, sums = ops.image_metrics_u8(a.contiguous(), b.contiguous(), crop)          # (checks dtypes, shapes and devices)
+    B, H, W, C = a.shape
+    ssd, sums = ssd.cpu().tolist(), sums.cpu().tolist()
+    rows = [_figures(ssd[i], sums[i], H - 2 * crop, W - 2 * crop, C) for i in range(B)]
+    return rows[0] if single else rows
+
+
+def test_u8(net, frames, scale, crop_border=None, num_masks=10, fixed_range=False, use_graph=False, soft_masks=None,
+            self_ensemble=False, names=None, results_file=None):
+    """The loop of the reference's test script (codes/test.py:62-152) for a video source.  ``frames`` is what
+    ``validate_u8`` takes: it yields ``(LQ, GT, Depth)`` with ``LQ`` a ``uint8`` ``[1,h,w,3]`` (or ``[h,w,3]``) BGR frame,
+    ``GT`` the ``[1,3,sh,sw]`` float tensor and ``Depth`` ``[1,1,h,w]``; further items are ignored.  SR comes from
+    ``video.FrameUpscaler`` (``num_masks`` ... ``self_ensemble`` are its arguments), GT is quantised by ``frame_emit_u8``
+    as in ``validate_u8``, and every frame's four figures are ``image_metrics`` of the two uint8 images with
+    ``crop_border`` pixels cropped (None: ``scale``, test.py:103; 0: no crop).  Nothing is read back per frame: the sums of
+    ``ops.image_metrics_u8`` go into device chunks and come to the host in one transfer at the end.
+
+    Returns ``dict(rows=[(name, psnr, ssim, psnr_y, ssim_y), ...], psnr=, ssim=, psnr_y=, ssim_y=, n=)``: the averages are
+    the script's plain means (test.py:141-148; 0.0 without frames).  ``names``: one name per frame (default: the frame's
+    index, six digits).  ``results_file``: a path that gets the script's tab-separated lines, one per frame and the
+    ``Average`` line (test.py:133,152), six decimals."""
+    from . import ops
+    from .video import FrameUpscaler
+    up = FrameUpscaler(net, num_masks=num_masks, fixed_range=fixed_range, use_graph=use_graph, min_max=(0, 1),
+                       soft_masks=soft_masks, self_ensemble=self_ensemble)
+    dev = up.device
+    crop = int(scale) if crop_border is None else int(crop_border)
+    CHUNK = 256
+    chunks, shapes, labels = [], [], []  # int64 [4*CHUNK] each: ssd in the first quarter, the sums (float64 bits) behind it
+    names = None if names is None else iter(names)
+
+    def view(i):
+        if i // CHUNK >= len(chunks):
+            chunks.append(torch.zeros((4 * CHUNK,), dtype=torch.int64, device=dev))
+        buf, j = chunks[i // CHUNK], i % CHUNK
+        return buf[j:j + 1], buf[CHUNK:].view(torch.float64).view(CHUNK, 3)[j:j + 1]
+
+    inf = float("inf")
+    with torch.no_grad():
+        for i, item in enumerate(frames):
+            lq, gt, depth = item[0], item[1], item[2]
+            lq = lq if torch.is_tensor(lq) else torch.from_numpy(np.ascontiguousarray(lq))
+            sr_u8, _ = up.upscale_device(lq[None] if lq.dim() == 3 else lq, depth)     # on the device, nothing waited for
+            gt = gt[:1].to(dev).float().contiguous()
+            gt_u8 = ops.frame_emit_u8(ops.nchw_to_nhwc(gt), -inf, inf, (0, 1), swap_rb=True)
+            ops.image_metrics_u8(sr_u8[:1].contiguous(), gt_u8, crop=crop, out=view(i))
+            shapes.append(tuple(gt_u8.shape[1:]))
+            labels.append("%06d" % i if names is None else str(next(names)))
+    n = len(shapes)
+    rows = []
+    if n:
+        host = (chunks[0] if len(chunks) == 1 else torch.cat(chunks)).cpu()      # the one read-back
+        for i, (H, W, C) in enumerate(shapes):
+            buf, j = host[4 * CHUNK * (i // CHUNK):4 * CHUNK * (i // CHUNK + 1)], i % CHUNK
+            fig = _figures(int(buf[j]), buf[CHUNK:].view(torch.float64).view(CHUNK, 3)[j].tolist(), H - 2 * crop,
+                           W - 2 * crop, C)
+            rows.append((labels[i], fig["psnr"], fig["ssim"], fig["psnr_y"], fig["ssim_y"]))
+    out = dict(rows=rows, n=n)
+    for k, key in enumerate(("psnr", "ssim", "psnr_y", "ssim_y")):
+        out[key] = sum(r[k + 1] for r in rows) / n if n else 0.0
+    if results_file is not None:
+        with open(results_file, "w") as fh:
+            for r in rows:
+                fh.write("{}\t{:.6f}\t{:.6f}\t{:.6f}\t{:.6f}\n".format(*r))
+            if n:
+                fh.write("Average\t{:.6f}\t{:.6f}\t{:.6f}\t{:.6f}\n".format(out["psnr"], out["ssim"], out["psnr_y"],
+                                                                          out["ssim_y"]))
+    return out

@@ -581,6 +581,32 @@ int dasr_frame_emit_u8(const float* y_nhwc, unsigned char* frames, int B, int H,
 size_t dasr_frame_ssd_u8_workspace(int B, int H, int W, int C, int crop);
 int dasr_frame_ssd_u8(const unsigned char* a, const unsigned char* b, unsigned long long* ssd, void* workspace,
                       size_t workspace_bytes, int B, int H, int W, int C, int crop, void* stream);
+/* dasr_image_metrics_u8: the four figures of the reference's test script (codes/test.py:97-152) for two uint8 [B,H,W,C]
+ * image batches, C = 3 in BGR order (what dasr_frame_emit_u8 with swap_rb and cv2 produce) or C = 1, inside a crop-pixel
+ * border (rows / columns crop .. H-1-crop / W-1-crop; crop == 0: the whole image, test.py:105-107).  With Hc = H - 2 crop,
+ * Wc = W - 2 crop, per frame b:
+ *   ssd[b]      exact (unsigned 64-bit) sum of (a - b)^2 over the region and all channels: dasr_frame_ssd_u8's quantity,
+ *               the mse * count of calculate_psnr (utils/util.py:646-653)
+ *   sums[b][0]  sum over the region of (Ya - Yb)^2, Y = (24.966 B + 128.553 G + 65.481 R) / 255 + 16 on the [0, 255] scale,
+ *               not rounded: bgr2ycbcr(only_y=True) in its float branch (data/util.py:199-213; test.py:100-101 divides by
+ *               255 first); 0 for C = 1
+ *   sums[b][1]  sum of the SSIM map of utils/util.py:656-676 over its (Hc-10) x (Wc-10) x C positions (calculate_ssim,
+ *               utils/util.py:679-697, averages three identical calls of ssim on the 3-channel array, and cv2.filter2D
+ *               filters each channel by itself: the plain mean over positions and channels)
+ *   sums[b][2]  the same sum for the one-channel luma image; 0 for C = 1
+ * The SSIM map: window outer(k, k), k[i] = exp(-(i-5)^2 / (2 * 1.5^2)) normalised to sum 1 (cv2.getGaussianKernel(11, 1.5)),
+ * correlation over VALID positions only, C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2, moments mu1, mu2, E[x^2] - mu1^2,
+ * E[y^2] - mu2^2, E[xy] - mu1 mu2, map = ((2 mu1 mu2 + C1)(2 s12 + C2)) / ((mu1^2 + mu2^2 + C1)(s1 + s2 + C2)).  Luma,
+ * moments, map and sums are fp64 (the window is applied separably).  This is NOT dasr_ssim's number (zero padding, fp32,
+ * [0, 1] tensors).  PSNR = 20 log10(255 / sqrt(ssd / (Hc Wc C))), PSNR_Y likewise from sums[0] / (Hc Wc),
+ * SSIM = sums[1] / ((Hc-10)(Wc-10) C), SSIM_Y = sums[2] / ((Hc-10)(Wc-10)).
+ * C other than 1 or 3, Hc < 11 or Wc < 11: DASR_E_UNSUPPORTED (below 11 the reference's [5:-5] leaves an empty map and
+ * returns NaN; that is refused, not reproduced).  B <= 65535.  workspace: dasr_image_metrics_u8_workspace() bytes, 8-byte
+ * aligned (four partials per workgroup, added per frame in index order by a second launch; no atomics: a frame's result
+ * has the same bits in every run, alone or as any member of a batch). */
+size_t dasr_image_metrics_u8_workspace(int B, int H, int W, int C, int crop);
+int dasr_image_metrics_u8(const unsigned char* a, const unsigned char* b, unsigned long long* ssd, double* sums,
+                          void* workspace, size_t workspace_bytes, int B, int H, int W, int C, int crop, void* stream);
 
 /* ---- training batches from uint8 HR frames (csrc/batch.hip) --------------------------------------------------------
  * The image half of the reference's training loader (codes/data/LQGTker_Depth_dataset.py:145-199) on the device: the
