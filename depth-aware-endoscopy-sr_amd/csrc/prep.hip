@@ -123,8 +123,13 @@ __device__ __forceinline__ prep_soft_t prep_soft(float v, float lo, float interv
 // all K planes in one launch; a lane owns four consecutive pixels and writes, plane by plane, one 16-byte store where the
 // four are inside the map and their address is 16-byte aligned, scalar stores otherwise (the tail of a map whose size is
 // no multiple of 4, planes that start off the 16-byte grid).  Every element of masks is written, zeros included.
+// PAIR: the same launch also writes the pixel's pair encoding (include/dasr.h) - pair_k = k as a plain byte store, like the
+// region bytes of k_depth_bins, and pair_s = -s where the neighbour is k - 1 and s > 0, else s (so a pixel without a second
+// plane holds +0.0, never -0.0) - and masks may be NULL, in which case the planes are not written.
+template <bool PAIR>
 __global__ void __launch_bounds__(256) k_depth_soft(const float* __restrict__ depth, const float* __restrict__ ws,
-                                                    float* __restrict__ masks, int HW, int K, int nchunk, float width,
+                                                    float* __restrict__ masks, unsigned char* __restrict__ pair_k,
+                                                    float* __restrict__ pair_s, int HW, int K, int nchunk, float width,
                                                     int fixed_range) {
     __shared__ float s_range[2];
     const int b = blockIdx.y;
@@ -161,6 +166,24 @@ __global__ void __launch_bounds__(256) k_depth_soft(const float* __restrict__ de
         prep_soft_t e[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) e[j] = prep_soft(v[j], lo, interval, K, width);
+        if (PAIR) {
+            float o[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = (e[j].n < e[j].k && e[j].wn > 0.f) ? -e[j].wn : e[j].wn;
+            unsigned char* dk = pair_k + (size_t)b * HW + p0;
+            float* ds = pair_s + (size_t)b * HW + p0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (j < cnt) dk[j] = (unsigned char)e[j].k;
+            if (full && ((uintptr_t)ds & 15) == 0) {
+                *(float4*)ds = make_float4(o[0], o[1], o[2], o[3]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (j < cnt) ds[j] = o[j];
+            }
+            if (masks == nullptr) continue;
+        }
         for (int i = 0; i < K; ++i) {
             float o[4];
 #pragma unroll
@@ -206,9 +229,12 @@ extern "C" int dasr_depth_to_masks(const float* depth, const float* fixed_edges,
 
 extern "C" size_t dasr_depth_to_masks_soft_workspace(int B, int HW) { return dasr_depth_to_masks_workspace(B, HW); }
 
-extern "C" int dasr_depth_to_masks_soft(const float* depth, float* masks, void* workspace, size_t workspace_bytes, int B,
-                                        int HW, int K, float width, int fixed_range, void* stream) {
-    DASR_CHECK_PTR(depth); DASR_CHECK_PTR(masks); DASR_CHECK_PTR(workspace);
+template <bool PAIR>
+static int depth_soft_impl(const float* depth, float* masks, unsigned char* pair_k, float* pair_s, void* workspace,
+                           size_t workspace_bytes, int B, int HW, int K, float width, int fixed_range, void* stream) {
+    DASR_CHECK_PTR(depth); DASR_CHECK_PTR(workspace);
+    if (PAIR) { DASR_CHECK_PTR(pair_k); DASR_CHECK_PTR(pair_s); }
+    else DASR_CHECK_PTR(masks);
     DASR_CHECK_SHAPE(B > 0 && HW > 0 && K > 0);
     if (K > PREP_MAXK) return DASR_E_UNSUPPORTED;
     DASR_CHECK_SHAPE(width > 0.f && width <= 1.f);                        // false for NaN too
@@ -218,7 +244,20 @@ extern "C" int dasr_depth_to_masks_soft(const float* depth, float* masks, void* 
         DASR_LAUNCH(k_depth_minmax, dim3(nchunk, B), dim3(256), 0, stream, depth, (float*)workspace, HW, nchunk);
     unsigned gx = dasr_cdiv(((size_t)HW + 3) / 4, 256);                   // a lane owns four pixels
     if (gx > 1024) gx = 1024;
-    DASR_LAUNCH(k_depth_soft, dim3(gx, B), dim3(256), 0, stream, depth, (const float*)workspace, masks, HW, K, nchunk, width,
-                fixed_range != 0 ? 1 : 0);
+    DASR_LAUNCH((k_depth_soft<PAIR>), dim3(gx, B), dim3(256), 0, stream, depth, (const float*)workspace, masks, pair_k, pair_s,
+                HW, K, nchunk, width, fixed_range != 0 ? 1 : 0);
     DASR_RETURN_LAUNCH_STATUS();
+}
+
+extern "C" int dasr_depth_to_masks_soft(const float* depth, float* masks, void* workspace, size_t workspace_bytes, int B,
+                                        int HW, int K, float width, int fixed_range, void* stream) {
+    return depth_soft_impl<false>(depth, masks, nullptr, nullptr, workspace, workspace_bytes, B, HW, K, width, fixed_range,
+                                  stream);
+}
+
+extern "C" int dasr_depth_to_masks_soft_pair(const float* depth, float* masks, unsigned char* pair_k, float* pair_s,
+                                             void* workspace, size_t workspace_bytes, int B, int HW, int K, float width,
+                                             int fixed_range, void* stream) {
+    return depth_soft_impl<true>(depth, masks, pair_k, pair_s, workspace, workspace_bytes, B, HW, K, width, fixed_range,
+                                 stream);
 }

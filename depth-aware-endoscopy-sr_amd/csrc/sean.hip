@@ -648,6 +648,232 @@ __global__ void __launch_bounds__(256, HAS_RES ? DASR_SEAN_RES_OCC : 3) k_sean_f
     if (AMAX) dasr_amax_commit(amax, om, sD, dasr_flat_wg(), dasr_flat_nwg());     // (sD: dead after the last tile)
 }
 
+// ---- forward, two-plane soft masks in the pair encoding (include/dasr.h) --------------------------------------------------
+// The producer's soft masks (csrc/prep.hip) have at most two non-zero planes per pixel and the two are neighbours: pair_k is
+// the plane that holds 1 - |pair_s|, the sign of pair_s picks the neighbour that holds |pair_s|.  The dynamic convolution is
+// then two row gathers per tap and table instead of the 9K-term GEMM of k_sean_fwd_soft, in that kernel's order of summation
+// (taps 0..8, the two planes of a tap in ascending plane index, fmaf chain from 0, bias added after the chain) and with its
+// modulation expression, so both evaluate the same function.  The structure is k_sean_fwd_onehot's: persistent workgroups,
+// D[b] with a zero row K in LDS (no bias folding here), 4 channels per lane, two register buffers of clamped loads.
+// A byte >= K, or a neighbour outside 0..K-1, reads the zero row: such a value is never an address.
+// byte tile and pair_s tile with a 1-pixel halo; outside the image the byte is K and s is 0
+__device__ __forceinline__ void sean_stage_P(const SeanGeom& g, const unsigned char* __restrict__ pair_k,
+                                             const float* __restrict__ pair_s, unsigned char* sR, float* sS, int b, int y0,
+                                             int x0, int TH) {
+    const int n = (TH + 2) * (SF_TW + 2);
+    for (int i0 = threadIdx.x; i0 < n; i0 += 2 * blockDim.x) {
+        unsigned char v[2];
+        float s[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int i = i0 + u * blockDim.x;
+            const int gy = y0 + i / (SF_TW + 2) - 1, gx = x0 + i % (SF_TW + 2) - 1;
+            v[u] = (unsigned char)g.K;
+            s[u] = 0.f;
+            if (i < n && gy >= 0 && gy < g.H && gx >= 0 && gx < g.W) {
+                const size_t p = ((size_t)b * g.H + gy) * g.W + gx;
+                v[u] = pair_k[p];
+                s[u] = pair_s[p];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int i = i0 + u * blockDim.x;
+            if (i < n) { sR[i] = v[u]; sS[i] = s[u]; }
+        }
+    }
+}
+__device__ __forceinline__ float4 f4fma(float w, float4 d, float4 a) {
+    return make_float4(fmaf(w, d.x, a.x), fmaf(w, d.y, a.y), fmaf(w, d.z, a.z), fmaf(w, d.w, a.w));
+}
+// gamma1 / beta1 WITHOUT bias of tile-local pixel (ly, lx).  Where the nine taps of every lane of the wave have s == 0 the
+// chain is acc = fmaf(1, D[k], acc) = acc + D[k] (and fmaf(0, D[n], acc) = acc for finite D): one row per tap, the same bits.
+// The scheduling barriers bound the rows in registers at a time to those of one tap (three on the one-row path).
+__device__ __forceinline__ void sean_gather_pair(const float* sD, const unsigned char* sR, const float* sS, int K, int K1,
+                                                 int ly, int lx, int cq, float4& g1, float4& b1) {
+    const unsigned char* pk = sR + ly * (SF_TW + 2) + lx;
+    const float* psv = sS + ly * (SF_TW + 2) + lx;
+    bool hard = true;
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) hard = hard && psv[(tap / 3) * (SF_TW + 2) + tap % 3] == 0.f;
+    float4 ag = make_float4(0.f, 0.f, 0.f, 0.f), ab = ag;
+    if (__all(hard ? 1 : 0)) {
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            const int rk = imin(pk[(tap / 3) * (SF_TW + 2) + tap % 3], K);
+            ag = f4add(ag, *(const float4*)(sD + ((0 * 9 + tap) * K1 + rk) * 64 + 4 * cq));
+            ab = f4add(ab, *(const float4*)(sD + ((1 * 9 + tap) * K1 + rk) * 64 + 4 * cq));
+            if (tap % 3 == 2) DASR_SCHED_BARRIER();
+        }
+        g1 = ag;
+        b1 = ab;
+        return;
+    }
+    // (k and s are read again tap by tap rather than kept: 18 registers the streaming buffers need more)
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) {
+        const int k = pk[(tap / 3) * (SF_TW + 2) + tap % 3];
+        const float sv = psv[(tap / 3) * (SF_TW + 2) + tap % 3];
+        const float a = fabsf(sv), wk = 1.f - a;                    // plane[k] = fl32(1 - |s|), plane[n] = |s|
+        const bool neg = sv < 0.f;
+        const int n = neg ? k - 1 : k + 1;
+        const int rk = imin(k, K), rn = (n >= 0 && n < K) ? n : K;
+        const int r0 = neg ? rn : rk, r1 = neg ? rk : rn;           // ascending plane index
+        const float w0 = neg ? a : wk, w1 = neg ? wk : a;
+        const float* dg = sD + (0 * 9 + tap) * K1 * 64 + 4 * cq;
+        const float* db = sD + (1 * 9 + tap) * K1 * 64 + 4 * cq;
+        ag = f4fma(w0, *(const float4*)(dg + r0 * 64), ag);
+        ag = f4fma(w1, *(const float4*)(dg + r1 * 64), ag);
+        ab = f4fma(w0, *(const float4*)(db + r0 * 64), ab);
+        ab = f4fma(w1, *(const float4*)(db + r1 * 64), ab);
+        DASR_SCHED_BARRIER();
+    }
+    g1 = ag;
+    b1 = ab;
+}
+__host__ __device__ constexpr int sean_pair_tile_px(void) { return (SF_TH + 2) * (SF_TW + 2); }
+// LDS bytes: D [18][K+1][64] floats | pair_s tile floats | byte tile
+__host__ __device__ constexpr int sean_pair_lds_bytes(int K) { return 4 * (18 * (K + 1) * 64 + sean_pair_tile_px()) + sean_pair_tile_px(); }
+
+template <bool RELU, bool HAS_RES, typename TA, bool AMAX = false>
+__global__ void __launch_bounds__(256, HAS_RES ? DASR_SEAN_RES_OCC : 3) k_sean_fwd_pair(SeanGeom g, const TA* __restrict__ t,
+                                                            const float* __restrict__ mean,
+                                                            const float* __restrict__ var,
+                                                            const TA* __restrict__ gb2,
+                                                            const unsigned char* __restrict__ pair_k,
+                                                            const float* __restrict__ pair_s, const float* __restrict__ D,
+                                                            const float* __restrict__ bias_g,
+                                                            const float* __restrict__ bias_b,
+                                                            const float* __restrict__ alpha_g,
+                                                            const float* __restrict__ alpha_b,
+                                                            const TA* __restrict__ residual,
+                                                            TA* __restrict__ out, float eps, int tiles_per_wg,
+                                                            float* __restrict__ amax) {
+    DASR_DYN_SMEM(smem);
+    constexpr int TH = SF_TH, NG = TH;                         // NG groups of 8 pixels per wave and tile (TH/4 rows x 4)
+    const int K1 = g.K + 1;
+    float* sD = (float*)smem;                                  // [18][K+1][64]
+    float* sS = sD + 18 * K1 * 64;                             // [(TH+2)*(TW+2)] pair_s
+    unsigned char* sR = (unsigned char*)(sS + sean_pair_tile_px());   // [(TH+2)*(TW+2)] pair_k
+    const int tiles_x = (g.W + SF_TW - 1) / SF_TW, tiles_y = (g.H + TH - 1) / TH;
+    const int tiles_per_sample = tiles_x * tiles_y;
+    const int c0 = blockIdx.y * 64;
+    const int lane = threadIdx.x & 63, wv = DASR_UNIFORM((int)(threadIdx.x >> 6));
+    const int cq = lane & 15, ps = lane >> 4;
+    const bool live = c0 + 4 * cq < g.C;
+    const int c = live ? c0 + 4 * cq : 0;                      // dead lanes (C % 64 != 0) shadow channel 0, never store
+    // persistent workgroup over a contiguous chunk of (sample, tile) pairs; tiles_per_wg packs (base, rem) as in
+    // k_sean_fwd_onehot: the first `rem` workgroups take base + 1 tiles
+    const int base = tiles_per_wg >> 16, rem = tiles_per_wg & 0xffff;
+    const int first = blockIdx.x * base + ((int)blockIdx.x < rem ? (int)blockIdx.x : rem);
+    int last = first + base + ((int)blockIdx.x < rem ? 1 : 0);
+    if (last > g.B * tiles_per_sample) last = g.B * tiles_per_sample;
+    if (first >= last) {
+        if (AMAX) dasr_amax_commit_idle(amax, dasr_flat_wg(), dasr_flat_nwg());
+        return;
+    }
+    auto tile_of = [&](int tt) {
+        const int tile = tt % tiles_per_sample;
+        return SeanTile{tt / tiles_per_sample, (tile / tiles_x) * TH, (tile % tiles_x) * SF_TW};
+    };
+    struct Buf { float4 tv[2], g2[2], b2[2], rv[2]; };
+    auto issue = [&](const SeanTile& T, int grp, Buf& f) {
+        const int y = imin(T.y0 + wv + 4 * (grp >> 2), g.H - 1);                // wave-uniform
+        const size_t row = ((size_t)T.b * g.H + y) * g.W;                       // scalar
+        const char* trow = (const char*)(t + row * g.C);
+        const char* grow = (const char*)(gb2 + row * 2 * g.C);
+        const char* brow = grow + (size_t)g.C * sizeof(TA);                      // beta half of the (gamma2 | beta2) pair
+        const char* rrow = HAS_RES ? (const char*)(residual + row * g.C) : nullptr;
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const unsigned x = (unsigned)imin(T.x0 + 8 * (grp & 3) + 4 * u + ps, g.W - 1);
+            const unsigned ot = (x * (unsigned)g.C + (unsigned)c) * (unsigned)sizeof(TA);
+            const unsigned og = (x * 2u * (unsigned)g.C + (unsigned)c) * (unsigned)sizeof(TA);
+            f.tv[u] = ld4_nt((const TA*)(trow + ot));                            // streamed once: keep D / halos cached
+            f.g2[u] = ld4_nt((const TA*)(grow + og));
+            f.b2[u] = ld4_nt((const TA*)(brow + og));
+            if (HAS_RES) f.rv[u] = ld4((const TA*)(rrow + ot));
+        }
+    };
+    Buf fa, fb;
+    SeanTile T = tile_of(first);
+    issue(T, 0, fa);
+    const float a_g = alpha_g[0], a_b = alpha_b[0];
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 bg = *(const float4*)(bias_g + c), bb = *(const float4*)(bias_b + c);
+    int cur_b = -1;
+    float4 mu = zero4, sc = zero4;
+    float om = 0.f;                                        // (AMAX) running max |out| of this lane
+    for (int tt = first; tt < last; ++tt) {
+        const int b = T.b, y0 = T.y0, x0 = T.x0;
+        __syncthreads();                                   // previous tile is done with sR / sS (and sD)
+        if (b != cur_b) {
+            sean_stage_D<HAS_RES ? 2 : 4>(g, D, sD, b, c0);
+            cur_b = b;
+            if (live) {
+                mu = *(const float4*)(mean + (size_t)b * g.C + c);
+                const float4 vr = *(const float4*)(var + (size_t)b * g.C + c);
+                sc = make_float4(dasr_double_in_scale(vr.x, eps), dasr_double_in_scale(vr.y, eps),
+                                 dasr_double_in_scale(vr.z, eps), dasr_double_in_scale(vr.w, eps));
+            }
+        }
+        sean_stage_P(g, pair_k, pair_s, sR, sS, b, y0, x0, TH);
+        __syncthreads();
+        auto consume = [&](int grp, const Buf& f) {
+            const int ly = wv + 4 * (grp >> 2), y = y0 + ly;
+            const size_t row = ((size_t)b * g.H + imin(y, g.H - 1)) * g.W;
+            char* orow = (char*)(out + row * g.C);
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int lx = 8 * (grp & 3) + 4 * u + ps, x = x0 + lx;
+                float4 r1, r2;
+                sean_gather_pair(sD, sR, sS, g.K, K1, ly, lx, cq, r1, r2);
+                // the modulation as k_sean_fwd_soft writes it
+                const float g1[4] = {r1.x + bg.x, r1.y + bg.y, r1.z + bg.z, r1.w + bg.w};
+                const float b1[4] = {r2.x + bb.x, r2.y + bb.y, r2.z + bb.z, r2.w + bb.w};
+                const float tq[4] = {f.tv[u].x, f.tv[u].y, f.tv[u].z, f.tv[u].w};
+                const float g2q[4] = {f.g2[u].x, f.g2[u].y, f.g2[u].z, f.g2[u].w};
+                const float b2q[4] = {f.b2[u].x, f.b2[u].y, f.b2[u].z, f.b2[u].w};
+                const float muq[4] = {mu.x, mu.y, mu.z, mu.w}, scq[4] = {sc.x, sc.y, sc.z, sc.w};
+                const float rq[4] = {HAS_RES ? f.rv[u].x : 0.f, HAS_RES ? f.rv[u].y : 0.f, HAS_RES ? f.rv[u].z : 0.f,
+                                     HAS_RES ? f.rv[u].w : 0.f};
+                float o[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float gam = a_g * g1[j] + (1.f - a_g) * g2q[j];
+                    const float bet = a_b * b1[j] + (1.f - a_b) * b2q[j];
+                    const float xh = (tq[j] - muq[j]) * scq[j];
+                    o[j] = xh * (1.f + gam) + bet;
+                    if (HAS_RES) o[j] += rq[j];
+                    if (RELU) o[j] = o[j] <= 0.f ? 0.f : o[j];  // NaN stays NaN, as in F.relu
+                }
+                if (live && y < g.H && x < g.W) {
+                    const float4 o4 = make_float4(o[0], o[1], o[2], o[3]);
+                    if (AMAX) om = dasr_amax4(om, o4);     // only what is stored counts (see k_sean_fwd_onehot)
+                    TA* dst = (TA*)(orow + ((unsigned)x * (unsigned)g.C + (unsigned)c) * (unsigned)sizeof(TA));
+                    st4_nt(dst, o4);
+                }
+            }
+        };
+        // two statically named register buffers, as in k_sean_fwd_onehot: fa already holds group 0 of this tile
+#pragma unroll 1
+        for (int grp = 0; grp < NG - 2; grp += 2) {
+            issue(T, grp + 1, fb);
+            consume(grp, fa);
+            issue(T, grp + 2, fa);
+            consume(grp + 1, fb);
+        }
+        issue(T, NG - 1, fb);
+        consume(NG - 2, fa);
+        if (tt + 1 < last) {
+            T = tile_of(tt + 1);
+            issue(T, 0, fa);
+        }
+        consume(NG - 1, fb);
+    }
+    if (AMAX) dasr_amax_commit(amax, om, sD, dasr_flat_wg(), dasr_flat_nwg());     // (sD: dead after the last tile)
+}
+
 // ---- forward, one-hot, bf16 activations with EIGHT channels (16 bytes) per lane --------------------------------------
 // With 4 bf16 channels per lane a wave instruction moves 512 bytes, half of what the fp32 instantiation has in flight per
 // instruction - the bf16 forward sat at 0.57-0.66 of the HBM peak against 0.75-0.8.  Here a lane owns 8 channels of one pixel
@@ -1650,6 +1876,60 @@ extern "C" int dasr_sean_fwd_bf16(const unsigned short* t, const float* mean, co
     return sean_fwd_impl<bf16_t>((const bf16_t*)t, mean, var, (const bf16_t*)gb2, mask, region, onehot_flag, D, bias_g,
                                  bias_b, alpha_g, alpha_b, (const bf16_t*)residual, (bf16_t*)out, relu, B, H, W, C, K, eps,
                                  stream);
+}
+
+// Forward for masks in the pair encoding: k_sean_fwd_pair alone, dealt over the resident slots like the gather kernel.
+template <typename T>
+static int sean_fwd_pair_impl(const T* t, const float* mean, const float* var, const T* gb2, const unsigned char* pair_k,
+                              const float* pair_s, const float* D, const float* bias_g, const float* bias_b,
+                              const float* alpha_g, const float* alpha_b, const T* residual, T* out, int relu, int B, int H,
+                              int W, int C, int K, float eps, void* stream, float* out_amax = nullptr) {
+    DASR_CHECK_PTR(t); DASR_CHECK_PTR(mean); DASR_CHECK_PTR(var); DASR_CHECK_PTR(gb2); DASR_CHECK_PTR(pair_k);
+    DASR_CHECK_PTR(pair_s); DASR_CHECK_PTR(D); DASR_CHECK_PTR(bias_g); DASR_CHECK_PTR(bias_b); DASR_CHECK_PTR(alpha_g);
+    DASR_CHECK_PTR(alpha_b); DASR_CHECK_PTR(out);
+    DASR_CHECK_SHAPE(B > 0 && H > 0 && W > 0 && C > 0 && K > 0);
+    if (K > SEAN_MAXK || (C % 4) != 0) return DASR_E_UNSUPPORTED;
+    SeanGeom g{B, H, W, C, K};
+    const int slices = (int)dasr_cdiv(C, 64);
+    const int tiles = B * ((W + SF_TW - 1) / SF_TW) * ((H + SF_TH - 1) / SF_TH);
+    int nwg = (residual ? 256 * DASR_SEAN_RES_OCC : 768) / slices;   // 256 CUs x 3 (2) resident workgroups, as the gather kernel
+    if (nwg < 1) nwg = 1;
+    if (nwg > tiles) nwg = tiles;
+    const int per = ((tiles / nwg) << 16) | (tiles % nwg);          // (base, rem), see the kernel; rem < nwg <= 768
+    const size_t lds = (size_t)sean_pair_lds_bytes(K);
+#define SEAN_PAIR_GO(RELU, RES)                                                                                        \
+    do {                                                                                                               \
+        if (sizeof(T) == 4 && out_amax != nullptr)                                                                     \
+            DASR_LAUNCH((k_sean_fwd_pair<RELU, RES, T, sizeof(T) == 4>), dim3(nwg, slices), dim3(256), lds, stream, g, t, \
+                        mean, var, gb2, pair_k, pair_s, D, bias_g, bias_b, alpha_g, alpha_b, residual, out, eps, per,   \
+                        out_amax);                                                                                     \
+        else                                                                                                           \
+            DASR_LAUNCH((k_sean_fwd_pair<RELU, RES, T>), dim3(nwg, slices), dim3(256), lds, stream, g, t, mean, var,    \
+                        gb2, pair_k, pair_s, D, bias_g, bias_b, alpha_g, alpha_b, residual, out, eps, per,              \
+                        (float*)nullptr);                                                                              \
+    } while (0)
+    if (relu) { if (residual) SEAN_PAIR_GO(true, true); else SEAN_PAIR_GO(true, false); }
+    else      { if (residual) SEAN_PAIR_GO(false, true); else SEAN_PAIR_GO(false, false); }
+#undef SEAN_PAIR_GO
+    DASR_RETURN_LAUNCH_STATUS();
+}
+
+extern "C" int dasr_sean_fwd_pair(const float* t, const float* mean, const float* var, const float* gb2,
+                                  const unsigned char* pair_k, const float* pair_s, const float* D, const float* bias_g,
+                                  const float* bias_b, const float* alpha_g, const float* alpha_b, const float* residual,
+                                  float* out, float* out_amax, int relu, int B, int H, int W, int C, int K, float eps,
+                                  void* stream) {
+    return sean_fwd_pair_impl<float>(t, mean, var, gb2, pair_k, pair_s, D, bias_g, bias_b, alpha_g, alpha_b, residual, out,
+                                     relu, B, H, W, C, K, eps, stream, out_amax);
+}
+extern "C" int dasr_sean_fwd_pair_bf16(const unsigned short* t, const float* mean, const float* var,
+                                       const unsigned short* gb2, const unsigned char* pair_k, const float* pair_s,
+                                       const float* D, const float* bias_g, const float* bias_b, const float* alpha_g,
+                                       const float* alpha_b, const unsigned short* residual, unsigned short* out, int relu,
+                                       int B, int H, int W, int C, int K, float eps, void* stream) {
+    return sean_fwd_pair_impl<bf16_t>((const bf16_t*)t, mean, var, (const bf16_t*)gb2, pair_k, pair_s, D, bias_g, bias_b,
+                                      alpha_g, alpha_b, (const bf16_t*)residual, (bf16_t*)out, relu, B, H, W, C, K, eps,
+                                      stream);
 }
 
 __global__ void __launch_bounds__(256) k_sean_bwd_zero(float* __restrict__ S, int nS, float* __restrict__ dbg,

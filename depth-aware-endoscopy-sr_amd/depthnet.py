@@ -138,13 +138,13 @@ def _device_guard(t):
 
 class _DepthNetFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, net, act_dtype, inp, depth_map, depth_mask, region, *params):
+    def forward(ctx, net, act_dtype, inp, depth_map, depth_mask, region, pair, *params):
         tape = Tape(enabled=True, act_dtype=act_dtype)
         tape.prepack = net._prepack_for(inp.device, act_dtype)
         pvars = [Var(p.detach(), p.requires_grad, name) for name, p in zip(net._param_names, params)]
         P = {v.name: v for v in pvars}
         out = graph.depthnet_forward(tape, P, net.cfg, net._consts(inp.device), inp.detach().contiguous(),
-                                     depth_map.detach().contiguous(), depth_mask.detach().contiguous(), region)
+                                     depth_map.detach().contiguous(), depth_mask.detach().contiguous(), region, pair)
         ctx.tape, ctx.pvars, ctx.out = tape, pvars, out
         ctx.hook = getattr(net, "_grad_bucket_hook", None)
         return out.data
@@ -168,7 +168,7 @@ class _DepthNetFunction(torch.autograd.Function):
         for v in pvars:
             v.grad = None
         ctx.tape = ctx.pvars = ctx.out = ctx.hook = None
-        return (None, None, None, None, None, None) + grads
+        return (None, None, None, None, None, None, None) + grads
 
 
 class DepthNet(nn.Module):
@@ -290,7 +290,7 @@ class DepthNet(nn.Module):
             tape.fold_cache = self._fold_cache
             P = {name: Var(p.detach(), False, name) for name, p in zip(self._param_names, params)}
             return graph.depthnet_infer_nhwc(tape, P, self.cfg, self._consts(x_nhwc.device), x_nhwc, depthMap, depthMask,
-                                             graph.attached_region(depthMask))
+                                             graph.attached_region(depthMask), graph.attached_pair(depthMask))
 
     def forward(self, input, depthMap, depthMask):
         with _device_guard(input):
@@ -311,9 +311,10 @@ class DepthNet(nn.Module):
         # masks prepared on the device (dasr_amd.prep.depth_to_masks) carry their region bytes: no compression pass,
         # no host read-back of the one-hot flag
         region = graph.attached_region(depthMask)
+        pair = graph.attached_pair(depthMask)         # soft masks from prep.depth_to_soft_masks(pair=True)
         act_dtype = self._act_dtype(input.device)
         if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-            return _DepthNetFunction.apply(self, act_dtype, input, depthMap, depthMask, region, *params)
+            return _DepthNetFunction.apply(self, act_dtype, input, depthMap, depthMask, region, pair, *params)
         tape = Tape(enabled=False, act_dtype=act_dtype)
         if not self.training:                 # netG.eval() + no_grad (F_model_depthCond.test): fold weights once
             if not hasattr(self, "_fold_cache"):
@@ -321,5 +322,5 @@ class DepthNet(nn.Module):
             tape.fold_cache = self._fold_cache
         P = {name: Var(p.detach(), False, name) for name, p in zip(self._param_names, params)}
         out = graph.depthnet_forward(tape, P, self.cfg, self._consts(input.device), input.detach().contiguous(),
-                                     depthMap.detach().contiguous(), depthMask.detach().contiguous(), region)
+                                     depthMap.detach().contiguous(), depthMask.detach().contiguous(), region, pair)
         return out.data

@@ -673,7 +673,8 @@ def dynk(tape, st, A_w, A_b, Wg, Wb):
 
 
 def sean_mod(tape, t, gb2, mask, D, bias_g, bias_b, alpha_g, alpha_b, residual, relu):
-    """``mask`` is a MaskPack (float planes + region index + one-hot flag)."""
+    """``mask`` is a MaskPack (float planes + region index + one-hot flag, or + the pair encoding of soft planes: the
+    forward is then the pair-gather kernel, the backward below the general one on the planes, unchanged)."""
     t.uses += 1
     gb2.uses += 1
     if residual is not None:
@@ -684,11 +685,16 @@ def sean_mod(tape, t, gb2, mask, D, bias_g, bias_b, alpha_g, alpha_b, residual, 
         # side stream's pool the moment the last SEAN's backward closure is dropped - while that backward may still be
         # queued - and the depth-branch backward that follows on the side stream allocates and writes into it (seen as a
         # wrong dD of the first depth block with half-resolution soft masks).
-        hand_over(gb2.event, gb2.data, mask.planes, mask.region)
+        hand_over(gb2.event, gb2.data, mask.planes, mask.region, mask.pair_k, mask.pair_s)
     mean, var = t.stats if t.stats is not None else ops.instnorm_stats(t.data)
-    y = ops.sean_fwd(t.data, mean, var, gb2.data, mask.planes, mask.region, mask.flag, D.data, bias_g.data, bias_b.data,
-                     alpha_g.data, alpha_b.data, residual.data if residual is not None else None, relu,
-                     amax=want_amax(tape, t.data))
+    if mask.pair_k is not None and t.data.shape[3] % 4 == 0:
+        y = ops.sean_fwd_pair(t.data, mean, var, gb2.data, mask.pair_k, mask.pair_s, D.data, bias_g.data, bias_b.data,
+                              alpha_g.data, alpha_b.data, residual.data if residual is not None else None, relu,
+                              amax=want_amax(tape, t.data))
+    else:
+        y = ops.sean_fwd(t.data, mean, var, gb2.data, mask.planes, mask.region, mask.flag, D.data, bias_g.data,
+                         bias_b.data, alpha_g.data, alpha_b.data, residual.data if residual is not None else None, relu,
+                         amax=want_amax(tape, t.data))
     out = Var(y, True)
 
     def bwd():
@@ -732,19 +738,42 @@ def attached_region(mask):
     return region
 
 
+def attached_pair(mask):
+    """``(pair_k, pair_s)`` that dasr_amd.prep.depth_to_soft_masks(pair=True) attached to a soft mask tensor, or None.
+    Trusted only while the tensor is unmodified, exactly as the region bytes above.  These are not region bytes: they
+    travel under their own names and only ``sean_mod``'s forward reads them."""
+    pair = getattr(mask, "_dasr_pair", None)
+    if pair is None:
+        return None
+    want = (mask.shape[0],) + tuple(mask.shape[2:])
+    if any(tuple(p.shape) != want or p.device != mask.device for p in pair):
+        return None
+    if getattr(mask, "_dasr_pair_version", None) != ops.tensor_version(mask):
+        return None
+    return pair
+
+
 class MaskPack:
     """The depth masks as the reference delivers them ([B,K,H,W] float planes) plus their compressed form
     (one region byte per pixel and a device-side "not one-hot" flag, dasr_mask_compress).
 
     The host never reads the flag: with (region, flag) both set every SEAN call launches the gather kernel and the
     general kernel and the flag decides ON THE DEVICE which of them works (the other returns at once); masks prepared
-    by prep.depth_to_masks are one-hot by construction (flag None: gather kernel only)."""
-    __slots__ = ("planes", "region", "flag", "_resized")
+    by prep.depth_to_masks are one-hot by construction (flag None: gather kernel only).
 
-    def __init__(self, planes, region=None, flag=None):
+    ``pair``: ``(pair_k, pair_s)`` of soft planes made by prep.depth_to_soft_masks(pair=True).  A pair pack has
+    region = flag = None (the backward takes the general kernels) and runs no compression pass."""
+    __slots__ = ("planes", "region", "flag", "pair_k", "pair_s", "_resized")
+
+    def __init__(self, planes, region=None, flag=None, pair=None):
         self.planes = planes
         self._resized = {}
+        self.pair_k, self.pair_s = None, None
         if FORCE_GENERAL_SEAN:               # tests: run the soft-mask kernels on one-hot masks (independent code path)
+            self.region, self.flag = None, None
+            return
+        if pair is not None:                 # soft planes with their pair encoding: no compression pass
+            self.pair_k, self.pair_s = pair
             self.region, self.flag = None, None
             return
         if region is not None:               # prepared on the device (one-hot by construction) or resized from a pack
@@ -763,7 +792,11 @@ class MaskPack:
         hit = self._resized.get((H, W))
         if hit is None:
             planes = ops.resize_nearest_nchw(self.planes, H, W)
-            if self.region is None:
+            if self.pair_k is not None:      # the decoding rule is pointwise: resizing the pair is resizing the planes
+                B = self.pair_s.shape[0]
+                pair_s = ops.resize_nearest_nchw(self.pair_s.view(B, 1, *self.pair_s.shape[1:]), H, W).view(B, H, W)
+                hit = MaskPack(planes, pair=(ops.resize_nearest_u8(self.pair_k, H, W), pair_s))
+            elif self.region is None:
                 hit = MaskPack(planes)
             else:
                 hit = MaskPack(planes, ops.resize_nearest_u8(self.region, H, W), self.flag)
@@ -903,17 +936,18 @@ def encoder_forward(tape, P, cfg, x0, depth_mask):
     return e1, e5, st
 
 
-def depthnet_forward(tape, P, cfg, consts, inp, depth_map, depth_mask, region=None):
+def depthnet_forward(tape, P, cfg, consts, inp, depth_map, depth_mask, region=None, pair=None):
     """DepthNet.forward (sftmd_arch.py:912-950). ``inp`` [B,3,H,W], ``depth_map`` [B,1,h,w],
     ``depth_mask`` [B,K,h,w] are the caller's NCHW tensors; returns (out NCHW tensor, out Var).
-    ``region``: the masks' region bytes [B,h,w] when they were prepared on the device (prep.depth_to_masks)."""
+    ``region``: the masks' region bytes [B,h,w] when they were prepared on the device (prep.depth_to_masks).
+    ``pair``: ``(pair_k, pair_s)`` of soft masks from prep.depth_to_soft_masks(pair=True) (``attached_pair``)."""
     pp = tape.prepack
     if pp is not None and not (PREPACK and tape.enabled and pp.lock.acquire(blocking=False)):
         pp = tape.prepack = None
     try:
         if pp is not None:
             pp.begin(P, Prepack.signature(inp, tape.act_dtype))
-        out = _depthnet_forward(tape, P, cfg, consts, inp, depth_map, depth_mask, region)
+        out = _depthnet_forward(tape, P, cfg, consts, inp, depth_map, depth_mask, region, pair=pair)
         if pp is not None:
             pp.finish()
         return out
@@ -922,7 +956,7 @@ def depthnet_forward(tape, P, cfg, consts, inp, depth_map, depth_mask, region=No
             pp.lock.release()
 
 
-def depthnet_infer_nhwc(tape, P, cfg, consts, x_nhwc, depth_map, depth_mask, region=None):
+def depthnet_infer_nhwc(tape, P, cfg, consts, x_nhwc, depth_map, depth_mask, region=None, pair=None):
     """The inference plan from an NHWC image: ``x_nhwc`` [B,H,W,3] float32 (what dasr_frame_ingest_u8 writes) instead of
     the reference's NCHW tensor; returns conv_output's NHWC result BEFORE the clamp of sftmd_arch.py:950 (what
     dasr_frame_emit_u8 reads).  The two layout passes of depthnet_forward are not run; every kernel in between is the
@@ -930,10 +964,10 @@ def depthnet_infer_nhwc(tape, P, cfg, consts, x_nhwc, depth_map, depth_mask, reg
     fold cache on the tape."""
     if tape.enabled:
         raise ValueError("depthnet_infer_nhwc is an inference entry: the tape must be off")
-    return _depthnet_forward(tape, P, cfg, consts, x_nhwc, depth_map, depth_mask, region, nhwc=True).data
+    return _depthnet_forward(tape, P, cfg, consts, x_nhwc, depth_map, depth_mask, region, nhwc=True, pair=pair).data
 
 
-def _depthnet_forward(tape, P, cfg, consts, inp, depth_map, depth_mask, region, *, nhwc=False):
+def _depthnet_forward(tape, P, cfg, consts, inp, depth_map, depth_mask, region, *, nhwc=False, pair=None):
     plan = block_plan(cfg)
     nb, scale = cfg["nb"], cfg["scale"]
     B = inp.shape[0]
@@ -941,7 +975,7 @@ def _depthnet_forward(tape, P, cfg, consts, inp, depth_map, depth_mask, region, 
     dm = Var(depth_map.reshape(B, depth_map.shape[2], depth_map.shape[3], 1))   # [B,1,h,w] == [B,h,w,1]
     L = ops.ACT_LRELU
     e1, _e5, st = encoder_forward(tape, P, cfg, x0, depth_mask)
-    mask_pack = MaskPack(depth_mask, region) if st is not None else None
+    mask_pack = MaskPack(depth_mask, region, pair=pair) if st is not None else None
     # head (:920).  Mixed precision: the encoder (0.8 % of the FLOPs, feeds the fp32 depth matrix) stays fp32; its first
     # feature map is rounded to bf16 here and everything up to conv_output's fp32 result runs on bf16 activations
     adt = tape.act_dtype
@@ -971,7 +1005,7 @@ def _depthnet_forward(tape, P, cfg, consts, inp, depth_map, depth_mask, region, 
             # no reference, so the last backward closure of the branch drops the last one - while the kernels it just
             # queued here have not run - and the head / encoder backward that follows on the main stream is handed the
             # block (seen as wrong mlp_mask.0.weight gradients of the first depth block, in whole-suite runs only).
-            hand_over(ready, dm.data, mask_pack.planes, mask_pack.region)
+            hand_over(ready, dm.data, mask_pack.planes, mask_pack.region, mask_pack.pair_k, mask_pack.pair_s)
             for i in executed:
                 name, kind, _ = plan[i]
                 if kind != "depth":

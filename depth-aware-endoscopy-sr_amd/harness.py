@@ -594,6 +594,14 @@ class Trainer:
                 if r_new is None or r_old is None:
                     raise ValueError("Trainer(use_graph=True): masks must be one-hot (prep.depth_to_masks / attach_region)")
                 r_old.copy_(r_new)
+            if self._static[3] is not masks and _g.attached_pair(self._static[3]) is not None:
+                # the captured forward reads the captured masks' pair side-cars: they travel with their mask tensor too
+                new = _g.attached_pair(masks)
+                if new is None:
+                    raise ValueError("Trainer(use_graph=True): the captured step reads a pair encoding; masks must come from "
+                                     "prep.depth_to_soft_masks(pair=True)")
+                for dst, src in zip(self._static[3]._dasr_pair, new):
+                    dst.copy_(src)
             for dst, src in zip(self._static, (lq, gt, depth, masks)):
                 if dst is not src:
                     if dst.shape != src.shape:
@@ -602,6 +610,8 @@ class Trainer:
                     dst.copy_(src)
             if self._static[3] is not masks:       # the copy bumped the captured mask tensor's version: re-stamp it
                 self._static[3]._dasr_version = _ops.tensor_version(self._static[3])
+                if getattr(self._static[3], "_dasr_pair", None) is not None:
+                    self._static[3]._dasr_pair_version = self._static[3]._dasr_version
         self._graph.replay()
         self.log = self._static_log
         return self.log

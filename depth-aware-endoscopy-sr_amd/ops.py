@@ -749,11 +749,13 @@ def depth_to_masks(depth, num_masks=10, fixed_edges=None, want_planes=True, out=
     return planes, region
 
 
-def depth_to_masks_soft(depth, num_masks=10, width=1.0, fixed_range=False, out=None):
+def depth_to_masks_soft(depth, num_masks=10, width=1.0, fixed_range=False, out=None, pair=False):
     """Soft (hat-function) membership planes (dasr_depth_to_masks_soft): depth [B,1,h,w] or [B,h,w] float32 -> planes
     [B,K,h,w] float32, at most two non-zero per pixel, summing to 1.  ``width`` in (0, 1]: the share of a bin over which
     two neighbours blend (1: linear interpolation between bin centres).  ``fixed_range``: bins over [0,1] instead of the
-    sample's own [min, max].  ``out``: a ``[B,K,h,w]`` buffer to write into instead of a new one."""
+    sample's own [min, max].  ``out``: a ``[B,K,h,w]`` buffer to write into instead of a new one.
+    ``pair=True`` (dasr_depth_to_masks_soft_pair, the same launch): returns ``(planes, pair_k, pair_s)`` - the planes, bit
+    for bit those of ``pair=False``, and their pair encoding (include/dasr.h), uint8 and float32 ``[B,h,w]``."""
     if depth.dtype != torch.float32:
         raise TypeError("depth_to_masks_soft: depth must be float32, got %s" % depth.dtype)
     if not 0.0 < float(width) <= 1.0:                    # False for NaN too
@@ -771,6 +773,12 @@ def depth_to_masks_soft(depth, num_masks=10, width=1.0, fixed_range=False, out=N
         planes = torch.empty((B, num_masks, h, w), dtype=torch.float32, device=d.device)
     nbytes = int(_lib.get().dasr_depth_to_masks_soft_workspace(B, h * w))
     ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=d.device)
+    if pair:
+        pair_k = torch.empty((B, h, w), dtype=torch.uint8, device=d.device)
+        pair_s = torch.empty((B, h, w), dtype=torch.float32, device=d.device)
+        _call("dasr_depth_to_masks_soft_pair", _p(d), _p(planes), _lib.ptr(pair_k, dtype=torch.uint8), _p(pair_s), _p(ws),
+              nbytes, B, h * w, int(num_masks), float(width), int(bool(fixed_range)))
+        return planes, pair_k, pair_s
     _call("dasr_depth_to_masks_soft", _p(d), _p(planes), _p(ws), nbytes, B, h * w, int(num_masks), float(width),
           int(bool(fixed_range)))
     return planes
@@ -793,6 +801,25 @@ def sean_fwd(t, mean, var, gb2, mask, region, flag, D, bias_g, bias_b, alpha_g, 
               _p(alpha_g), _p(alpha_b), _pa(residual, True), _pa(out), int(relu), B, H, W, C, K, IN_EPS)
     else:
         _call("dasr_sean_fwd", _p(t), _p(mean), _p(var), _p(gb2), _p(mask), rp, fp, _p(D), _p(bias_g), _p(bias_b),
+              _p(alpha_g), _p(alpha_b), _p(residual, True), _p(out), _p(amax, True), int(relu), B, H, W, C, K, IN_EPS)
+        set_amax(out, amax)
+    return out
+
+
+def sean_fwd_pair(t, mean, var, gb2, pair_k, pair_s, D, bias_g, bias_b, alpha_g, alpha_b, residual, relu, amax=None):
+    """``sean_fwd`` for a soft mask in the pair encoding (dasr_sean_fwd_pair[_bf16]): ``pair_k`` uint8 and ``pair_s``
+    float32 ``[B,H,W]`` instead of the planes.  Forward only - the backward is ``sean_bwd`` on the planes."""
+    B, H, W, C = t.shape
+    K = D.shape[3]
+    assert pair_k.shape == (B, H, W) and pair_s.shape == (B, H, W) and gb2.shape == (B, H, W, 2 * C)
+    assert D.shape == (B, 2, 9, K, C)
+    out = torch.empty_like(t)
+    kp = _lib.ptr(pair_k, dtype=torch.uint8)
+    if _is_bf(t, gb2, residual):
+        _call("dasr_sean_fwd_pair_bf16", _pa(t), _p(mean), _p(var), _pa(gb2), kp, _p(pair_s), _p(D), _p(bias_g), _p(bias_b),
+              _p(alpha_g), _p(alpha_b), _pa(residual, True), _pa(out), int(relu), B, H, W, C, K, IN_EPS)
+    else:
+        _call("dasr_sean_fwd_pair", _p(t), _p(mean), _p(var), _p(gb2), kp, _p(pair_s), _p(D), _p(bias_g), _p(bias_b),
               _p(alpha_g), _p(alpha_b), _p(residual, True), _p(out), _p(amax, True), int(relu), B, H, W, C, K, IN_EPS)
         set_amax(out, amax)
     return out

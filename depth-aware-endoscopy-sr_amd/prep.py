@@ -65,7 +65,29 @@ def mark_soft(masks):
     return masks
 
 
-def depth_to_soft_masks(depth, num_masks=10, fixed_range=False, width=1.0):
+def _stamp_pair(masks, pair_k, pair_s):
+    """The pair encoding of soft ``masks`` (include/dasr.h), under its own names: these bytes are not region bytes and never
+    reach ``_dasr_region``.  Valid while the tensor is unmodified (``graph.attached_pair``)."""
+    masks._dasr_pair = (pair_k, pair_s)
+    masks._dasr_pair_version = ops.tensor_version(masks)
+
+
+def pair_planes(pair_k, pair_s, K):
+    """The decoding rule of the pair encoding (include/dasr.h) in torch: ``pair_k`` uint8, ``pair_s`` float32 ``[B,h,w]``
+    -> planes ``[B,K,h,w]`` float32.  ``plane[k] = fl32(1 - |s|)``, ``plane[n] = |s|`` with ``n = k - 1`` for a negative
+    ``s`` and ``k + 1`` otherwise, every other plane 0; a ``k >= K`` or an ``n`` outside ``0..K-1`` contributes nothing."""
+    k = pair_k.to(torch.int64)
+    a = pair_s.abs()
+    n = torch.where(pair_s < 0, k - 1, k + 1)
+    B, h, w = pair_k.shape
+    planes = torch.zeros((B, K + 1, h, w), dtype=torch.float32, device=pair_s.device)   # plane K collects what is dropped
+    kn = torch.where((n >= 0) & (n < K), n, torch.full_like(n, K))
+    planes.scatter_(1, kn.unsqueeze(1), a.unsqueeze(1))
+    planes.scatter_(1, k.clamp(max=K).unsqueeze(1), (1.0 - a).unsqueeze(1))
+    return planes[:, :K].contiguous()
+
+
+def depth_to_soft_masks(depth, num_masks=10, fixed_range=False, width=1.0, pair=False):
     """``depth`` ``[B,1,h,w]`` (or ``[B,h,w]``) float32 -> soft ``DepthMaskList`` ``[B,K,h,w]`` float32: hat-function
     membership in the K depth bins of ``depth_to_masks`` (``dasr_depth_to_masks_soft``; the rule is in include/dasr.h).
     ``width`` in (0, 1] is the share of a bin over which two neighbouring regions blend: 1 interpolates linearly between
@@ -75,8 +97,18 @@ def depth_to_soft_masks(depth, num_masks=10, fixed_range=False, width=1.0):
 
     The result is stamped like ``mark_soft`` output: ``attach_region`` answers False at once, so ``harness.fused_losses``
     and a ``Trainer`` step (eager or captured) take the general (soft-mask) kernels without a compression pass of their
-    own and without reading a flag back."""
+    own and without reading a flag back.
+
+    ``pair=True``: the same launch also writes the masks' pair encoding (include/dasr.h) and the planes carry it, stamped with
+    their version like the region bytes of ``depth_to_masks``: ``DepthNet`` then runs the pair-gather SEAN forward
+    (``dasr_sean_fwd_pair``) instead of the general one; the backward and the losses read the planes as before.  An
+    in-place edit of the planes drops the pair (and the soft stamp)."""
     # (the op raises TypeError for a depth that is not float32, ValueError for a width outside (0, 1] or more than 16 masks)
+    if pair:
+        planes, pair_k, pair_s = ops.depth_to_masks_soft(depth, int(num_masks), float(width), bool(fixed_range), pair=True)
+        _stamp(planes, None, True)
+        _stamp_pair(planes, pair_k, pair_s)
+        return planes
     planes = ops.depth_to_masks_soft(depth, int(num_masks), float(width), bool(fixed_range))
     _stamp(planes, None, True)
     return planes

@@ -148,7 +148,7 @@ def validate(net, frames, scale):
 
 
 def validate_u8(net, frames, scale, num_masks=10, fixed_range=False, use_graph=False, soft_masks=None,
-                self_ensemble=False):
+                self_ensemble=False, soft_pair=False):
     """The loop of ``validate()`` for a video source: ``frames`` yields ``(LQ, GT, Depth)`` with ``LQ`` a ``uint8``
     ``[1,h,w,3]`` (or ``[h,w,3]``) BGR frame as ``cv2`` reads it, ``GT`` the ``[1,3,sh,sw]`` float tensor and ``Depth``
     ``[1,1,h,w]``; a fourth item (the reference loader's mask list) is ignored, the masks are binned on the device.
@@ -157,12 +157,12 @@ def validate_u8(net, frames, scale, num_masks=10, fixed_range=False, use_graph=F
     ``scale``-pixel border cropped (``dasr_frame_ssd_u8``; ``inf`` at ``ssd == 0``); SSIM is ``dasr_ssim`` of the [0,1]
     tensors as in ``validate()``.  Nothing is read back per frame: the sums stay on the device and come to the host in
     one transfer at the end.  ``soft_masks``: ``FrameUpscaler``'s (None: one-hot masks; a number: soft masks of that blend
-    width).  ``self_ensemble``: ``FrameUpscaler``'s - SR is then ``test_x8``'s geometric self-ensemble, the figures of a
+    width; ``soft_pair``: its pair-gather forward for them).  ``self_ensemble``: ``FrameUpscaler``'s - SR is then ``test_x8``'s geometric self-ensemble, the figures of a
     paper's "+" rows.  Returns (avg_psnr, avg_ssim, n)."""
     from . import ops
     from .video import FrameUpscaler
     up = FrameUpscaler(net, num_masks=num_masks, fixed_range=fixed_range, use_graph=use_graph, min_max=(0, 1),
-                       soft_masks=soft_masks, self_ensemble=self_ensemble)
+                       soft_masks=soft_masks, self_ensemble=self_ensemble, soft_pair=soft_pair)
     dev = up.device
     CHUNK = 256
     chunks, counts = [], []              # int64 [2*CHUNK] each: ssd in the first half, ssim (float32 bits) in the second
@@ -238,11 +238,11 @@ def image_metrics(sr_u8, gt_u8, crop_border):
 
 
 def test_u8(net, frames, scale, crop_border=None, num_masks=10, fixed_range=False, use_graph=False, soft_masks=None,
-            self_ensemble=False, names=None, results_file=None):
+            self_ensemble=False, names=None, results_file=None, soft_pair=False):
     """The loop of the reference's test script (codes/test.py:62-152) for a video source.  ``frames`` is what
     ``validate_u8`` takes: it yields ``(LQ, GT, Depth)`` with ``LQ`` a ``uint8`` ``[1,h,w,3]`` (or ``[h,w,3]``) BGR frame,
     ``GT`` the ``[1,3,sh,sw]`` float tensor and ``Depth`` ``[1,1,h,w]``; further items are ignored.  SR comes from
-    ``video.FrameUpscaler`` (``num_masks`` ... ``self_ensemble`` are its arguments), GT is quantised by ``frame_emit_u8``
+    ``video.FrameUpscaler`` (``num_masks`` ... ``self_ensemble`` and ``soft_pair`` are its arguments), GT is quantised by ``frame_emit_u8``
     as in ``validate_u8``, and every frame's four figures are ``image_metrics`` of the two uint8 images with
     ``crop_border`` pixels cropped (None: ``scale``, test.py:103; 0: no crop).  Nothing is read back per frame: the sums of
     ``ops.image_metrics_u8`` go into device chunks and come to the host in one transfer at the end.
@@ -254,7 +254,7 @@ def test_u8(net, frames, scale, crop_border=None, num_masks=10, fixed_range=Fals
     from . import ops
     from .video import FrameUpscaler
     up = FrameUpscaler(net, num_masks=num_masks, fixed_range=fixed_range, use_graph=use_graph, min_max=(0, 1),
-                       soft_masks=soft_masks, self_ensemble=self_ensemble)
+                       soft_masks=soft_masks, self_ensemble=self_ensemble, soft_pair=soft_pair)
     dev = up.device
     crop = int(scale) if crop_border is None else int(crop_border)
     CHUNK = 256

@@ -77,6 +77,11 @@ class FrameUpscaler:
     is then what ``validate.test`` gives with ``prep.depth_to_soft_masks(depth, num_masks, fixed_range, width)``.  It is a
     constructor constant (not part of a captured graph's signature).
 
+    ``soft_pair=True`` (with ``soft_masks`` only, else ``ValueError``; a constructor constant too): the binning launch also
+    writes the planes' pair encoding (``dasr_depth_to_masks_soft_pair``) and every SEAN forward is the pair-gather kernel
+    (``dasr_sean_fwd_pair``) - the same function of the same planes as the general kernel, summed in the same order, at
+    two table rows per tap instead of ``9 * num_masks`` terms.  Opt-in; the default runs the general kernels as before.
+
     ``self_ensemble=True``: geometric self-ensemble, ``validate.test_x8`` per frame - the result is, byte for byte,
     ``tensor2img(validate.test_x8(net, img2tensor(frames), depth, masks)[b])``.  The chain ingests the frame into its eight
     flip / transpose members (``dasr_ensemble_ingest_u8``), expands the depth map, bins the masks from the expanded depth
@@ -94,7 +99,7 @@ class FrameUpscaler:
     input shape (two when ``upscale_iter`` is used), for the ``max_shapes`` most recently used shapes."""
 
     def __init__(self, net, num_masks=10, fixed_range=False, use_graph=True, min_max=(0, 1), max_shapes=4, soft_masks=None,
-                 self_ensemble=False):
+                 self_ensemble=False, soft_pair=False):
         self.net = net
         self.self_ensemble = bool(self_ensemble)
         self.num_masks = int(num_masks)
@@ -102,6 +107,9 @@ class FrameUpscaler:
         self.soft_masks = None if soft_masks is None else float(soft_masks)
         if self.soft_masks is not None and not 0.0 < self.soft_masks <= 1.0:
             raise ValueError("FrameUpscaler: soft_masks is the blend width, in (0, 1], got %r" % (soft_masks,))
+        self.soft_pair = bool(soft_pair)
+        if self.soft_pair and self.soft_masks is None:
+            raise ValueError("FrameUpscaler: soft_pair is meaningful with soft_masks=WIDTH only")
         self.min_max = (min_max[0], min_max[1])
         p = next(net.parameters())
         self.device = p.device
@@ -136,7 +144,9 @@ class FrameUpscaler:
 
     # ---- the chain -----------------------------------------------------------------------------------------------------
     def _masks(self, depth):
-        if self.soft_masks is not None:
+        if self.soft_pair:                               # as prep.depth_to_soft_masks(pair=True): planes and pair, one launch
+            planes = prep.depth_to_soft_masks(depth, self.num_masks, self.fixed_range, self.soft_masks, pair=True)
+        elif self.soft_masks is not None:
             planes = ops.depth_to_masks_soft(depth, self.num_masks, self.soft_masks, self.fixed_range)
             prep.mark_soft(planes)                       # as prep.depth_to_soft_masks: the general kernels, no read-back
         else:

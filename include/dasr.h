@@ -381,6 +381,41 @@ size_t dasr_depth_to_masks_soft_workspace(int B, int HW);
 int dasr_depth_to_masks_soft(const float* depth, float* masks, void* workspace, size_t workspace_bytes, int B, int HW,
                              int K, float width, int fixed_range, void* stream);
 
+/* ---- the pair encoding of a soft mask made by the rule above ------------------------------------------------------
+ * At most two planes of such a mask are non-zero per pixel and the two are neighbours, so a pixel is described by two
+ * side-cars next to the K planes:
+ *   pair_k  uint8   [B,HW]  the plane k that holds 1 - s (the k of the rule); byte K = "no plane"
+ *   pair_s  float32 [B,HW]  |pair_s| = s in [0, 0.5]; negative: the neighbour is n = k - 1, otherwise n = k + 1.
+ *                           A pixel without a second plane (a bin centre, an end plane facing outwards, a constant
+ *                           map) has s == 0, stored as +0.0 and never -0.0.
+ * Decoding (THE rule, dasr_amd.prep.pair_planes restates it):
+ *   plane[k] = fl32(1 - |pair_s|)  (the producer's own rounding of 1 - s),  plane[n] = |pair_s|,  every other plane 0;
+ *   a k >= K, or an n outside 0..K-1, contributes nothing for that term - it is never used as an address.
+ * These bytes are NOT the one-hot region bytes of dasr_mask_compress / dasr_depth_to_masks: they go to
+ * dasr_sean_fwd_pair[_bf16] only, never to dasr_sean_bwd, the loss kernels or any `region` argument.
+ *
+ * dasr_depth_to_masks_soft_pair: dasr_depth_to_masks_soft with the two side-cars written by the same launch.  masks may
+ * be NULL (the planes are then not written); pair_k and pair_s are required (DASR_E_NULL).  The planes are bit-identical
+ * to dasr_depth_to_masks_soft's; refusals and workspace (dasr_depth_to_masks_soft_workspace) are the same. */
+int dasr_depth_to_masks_soft_pair(const float* depth, float* masks, unsigned char* pair_k, float* pair_s, void* workspace,
+                                  size_t workspace_bytes, int B, int HW, int K, float width, int fixed_range, void* stream);
+
+/* dasr_sean_fwd for a mask in the pair encoding: the arguments of dasr_sean_fwd with (mask, region, onehot_flag)
+ * replaced by (pair_k, pair_s) [B,H,W].  Computes what dasr_sean_fwd computes on the decoded planes, in the general
+ * kernel's order of summation (taps 0..8, the two planes of a tap in ascending plane index, the bias after the chain),
+ * with two row gathers per tap instead of the 9K-term contraction.  Forward only: the backward is dasr_sean_bwd on the
+ * planes with region = onehot_flag = NULL.  C % 4 != 0 or K > 16: DASR_E_UNSUPPORTED before any launch.
+ * out_amax (fp32 entry point, may be NULL): as in dasr_sean_fwd, kept by the kernel itself. */
+int dasr_sean_fwd_pair(const float* t, const float* mean, const float* var, const float* gb2, const unsigned char* pair_k,
+                       const float* pair_s, const float* D, const float* bias_gamma, const float* bias_beta,
+                       const float* alpha_gamma, const float* alpha_beta, const float* residual, float* out,
+                       float* out_amax, int relu, int B, int H, int W, int C, int K, float eps, void* stream);
+int dasr_sean_fwd_pair_bf16(const unsigned short* t, const float* mean, const float* var, const unsigned short* gb2,
+                            const unsigned char* pair_k, const float* pair_s, const float* D, const float* bias_gamma,
+                            const float* bias_beta, const float* alpha_gamma, const float* alpha_beta,
+                            const unsigned short* residual, unsigned short* out, int relu, int B, int H, int W, int C,
+                            int K, float eps, void* stream);
+
 /* ---- harness losses in one pass (one-hot and soft masks) ----------------------------------
  * nn.L1Loss + dynamic_weight_mask_loss('smoothl1') (F_model_depthCond.py:164,188-190; mask_loss.py:64-90) need, per
  * depth region k, sum smooth_l1(m_k*sr, m_k*hr) and sum m_k (masks nearest-upsampled to HR), and sum |sr-hr|.

@@ -71,6 +71,37 @@ def bench_loss(a, dev, rounds=5):
     print("%-44s %9.1f us" % ("PyTorch formulation, soft masks: backward", fb - f))
 
 
+def bench_pair(a, dev, t, gb2, D, bg, bb, ag, ab, resid, mk, region, rounds=3):
+    """The pair-gather forward (dasr_sean_fwd_pair) against the general forward on the same producer-made soft masks (random
+    depth maps, width 1.0: nearly every pixel has two planes) and against the gather forward on the one-hot masks, in one
+    process: ``rounds`` alternating rounds of ``--iters`` calls each, fp32 and bf16, with and without the residual.  Prints
+    min / median / max per arm and one JSON line."""
+    import json
+    B, H, W, C = t.shape
+    K = D.shape[3]
+    depth = torch.rand(B, 1, H, W, device=dev)
+    planes, pk, ps = ops.depth_to_masks_soft(depth, K, 1.0, False, pair=True)
+    two = float((ps != 0).float().mean())
+    result = {"shape": [B, H, W, C, K], "width": 1.0, "pixels_with_two_planes": round(two, 4), "iters": a.iters, "arms": {}}
+    for dname, cast in (("fp32", lambda x: x), ("bf16", ops.cast_to_bf16)):
+        tt, gg, rr = cast(t), cast(gb2), cast(resid)
+        mean, var = ops.instnorm_stats(tt)
+        for rname, r in (("", None), ("+res", rr)):
+            arms = (("pair", lambda: ops.sean_fwd_pair(tt, mean, var, gg, pk, ps, D, bg, bb, ag, ab, r, True)),
+                    ("general", lambda: ops.sean_fwd(tt, mean, var, gg, planes, None, None, D, bg, bb, ag, ab, r, True)),
+                    ("gather (one-hot masks)", lambda: ops.sean_fwd(tt, mean, var, gg, mk, region, None, D, bg, bb, ag, ab, r, True)))
+            ts = {nm: [] for nm, _ in arms}
+            for _ in range(rounds):                       # alternating: every round times every arm once
+                for nm, fn in arms:
+                    ts[nm].append(timeit(fn, a.iters))
+            for nm, _ in arms:
+                v = sorted(ts[nm])
+                result["arms"]["%s%s %s" % (dname, rname, nm)] = {"min": round(v[0], 1), "median": round(v[len(v) // 2], 1),
+                                                                  "max": round(v[-1], 1)}
+                print("sean_fwd%-4s %-4s %-24s %8.1f us (%.1f .. %.1f)" % (rname, dname, nm, v[len(v) // 2], v[0], v[-1]), flush=True)
+    print(json.dumps({"soft_pair_ops": result}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=16)
@@ -124,6 +155,7 @@ def main():
                 us = timeit(lambda: ops.sean_bwd(dout, o, t, mean, var, gb2, m, None, None, D, bg, bb, ag, ab, True, True),
                             a.iters)
                 print("sean_bwd     general path, %-14s %8.1f us" % (name, us))
+            bench_pair(a, dev, t, gb2, D, bg, bb, ag, ab, resid, mk, region)
     if not a.only or "loss" in a.only:
         bench_loss(a, dev)
     if not a.only or "dynk" in a.only:

@@ -12,6 +12,8 @@
            mode under `rocprofv3 --kernel-trace --stats`.  The byte floor 4 (1 + K) B HW (+ 4 B HW for the min / max
            pass) is computed here from the shapes.
 
+--soft-pair (frames): a third upscaler in the same alternating rounds, soft masks with the pair-gather SEAN forward
+(FrameUpscaler(soft_pair=True)), with the share of the one-hot / soft gap it closes.
 --out merges the result into a JSON file."""
 import argparse
 import json
@@ -30,6 +32,8 @@ def main():
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     ap.add_argument("--mode", default="frames", choices=("frames", "kernels"))
     ap.add_argument("--soft-masks", type=float, default=1.0, metavar="WIDTH")
+    ap.add_argument("--soft-pair", action="store_true",
+                    help="frames: a third upscaler, soft masks with the pair-gather forward (soft_pair=True), in the same rounds")
     ap.add_argument("--dtypes", default="fp32,bf16")
     ap.add_argument("--frames", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
@@ -62,6 +66,8 @@ def main():
             net = net.to(dev).set_compute_dtype(dtype)
             ups = {"onehot": FrameUpscaler(net, num_masks=K, use_graph=True),
                    "soft": FrameUpscaler(net, num_masks=K, use_graph=True, soft_masks=a.soft_masks)}
+            if a.soft_pair:
+                ups["soft_pair"] = FrameUpscaler(net, num_masks=K, use_graph=True, soft_masks=a.soft_masks, soft_pair=True)
 
             def run(up, n):
                 t0 = time.perf_counter()
@@ -80,6 +86,13 @@ def main():
             result[dtype] = {k: dict(mmm(v), rounds_fps=v, graph_replays=ups[k].replays) for k, v in fps.items()}
             result[dtype]["soft_over_onehot_median"] = round(result[dtype]["soft"]["median"] / result[dtype]["onehot"]["median"], 4)
             result[dtype]["output_bytes_that_differ"] = differ
+            if a.soft_pair:
+                r = result[dtype]
+                ms = {k: 1e3 / r[k]["median"] for k in ups}
+                r["pair_over_soft_median"] = round(r["soft_pair"]["median"] / r["soft"]["median"], 4)
+                r["gap_closed"] = round((ms["soft"] - ms["soft_pair"]) / (ms["soft"] - ms["onehot"]), 4)   # of the ms per frame
+                r["pair_slowest_round_beats_soft_fastest"] = r["soft_pair"]["min"] > r["soft"]["max"]
+                r["pair_output_bytes_that_differ_from_soft"] = int((ups["soft"].upscale(*pool[0]) != ups["soft_pair"].upscale(*pool[0])).sum())
     else:
         B, h, w = 16, 128, 160
         HW = h * w

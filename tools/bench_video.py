@@ -7,7 +7,9 @@
   d  video.FrameUpscaler(use_graph=True).upscale_iter     (two-slot pipeline; per frame = time between two results)
 
 for one configuration (--config x8: the x8 net on a 128x160 frame; x2: the x2 net on a 540x960 frame; --dtype fp32|bf16;
---soft-masks WIDTH: soft depth masks of that blend width in every arm, default one-hot; its entry's key ends in _softWIDTH).
+--soft-masks WIDTH: soft depth masks of that blend width in every arm, default one-hot; its entry's key ends in _softWIDTH;
+--soft-pair with it: the pair-gather SEAN forward in arms b, c, d (arm a, the reference's call, keeps the general path; the
+byte-equality with b then holds to one unit); key ..._pair).
 tools/bench_soft_prep.py compares the two mask kinds in one process, alternating.
 --self-ensemble: arms b, c and d run a second time with FrameUpscaler(self_ensemble=True) (validate.test_x8 per frame: eight
 flip / transpose members, two forwards of batch 4) as arms b_x8ens, c_x8ens, d_x8ens, alternating with the plain arms in the
@@ -47,6 +49,8 @@ def main():
     ap.add_argument("--arms", default="abcd")
     ap.add_argument("--soft-masks", type=float, default=None, metavar="WIDTH",
                     help="soft depth masks of this blend width (prep.depth_to_soft_masks) in every arm; default: one-hot")
+    ap.add_argument("--soft-pair", action="store_true",
+                    help="with --soft-masks: the pair-gather SEAN forward (FrameUpscaler(soft_pair=True)) in arms b, c, d")
     ap.add_argument("--self-ensemble", action="store_true",
                     help="also time arms b, c, d with FrameUpscaler(self_ensemble=True); the entry's key ends in _x8ens")
     ap.add_argument("--out", default=None)
@@ -80,9 +84,10 @@ def main():
         return validate.tensor2img(sr[0])[None]                                # download + clamp / transpose / round on the host
 
     soft = a.soft_masks
-    up_b = FrameUpscaler(net, num_masks=K, use_graph=False, soft_masks=soft)
-    up_c = FrameUpscaler(net, num_masks=K, use_graph=True, soft_masks=soft)
-    up_d = FrameUpscaler(net, num_masks=K, use_graph=True, soft_masks=soft)
+    pair = dict(soft_pair=True) if a.soft_pair else {}       # (ValueError from the upscaler without --soft-masks)
+    up_b = FrameUpscaler(net, num_masks=K, use_graph=False, soft_masks=soft, **pair)
+    up_c = FrameUpscaler(net, num_masks=K, use_graph=True, soft_masks=soft, **pair)
+    up_d = FrameUpscaler(net, num_masks=K, use_graph=True, soft_masks=soft, **pair)
 
     def per_call(fn):
         def run(n):
@@ -113,7 +118,7 @@ def main():
     same = {k: bool(np.array_equal(fn(f0, d0), ref)) for k, fn in (("a", arm_a), ("c", up_c.upscale)) if k in arms}
     ens = {}
     if a.self_ensemble:
-        ens = {k: FrameUpscaler(net, num_masks=K, use_graph=k != "b", soft_masks=soft, self_ensemble=True)
+        ens = {k: FrameUpscaler(net, num_masks=K, use_graph=k != "b", soft_masks=soft, self_ensemble=True, **pair)
                for k in "bcd" if k in a.arms}
         for k, up in ens.items():
             arms[k + "_x8ens"] = pipelined(up) if k == "d" else per_call(up.upscale)
@@ -132,7 +137,7 @@ def main():
             torch.cuda.synchronize()
             allms[k] += ms
             rounds[k].append(stats(ms)["median_ms"])
-    entry = dict(config=a.config, dtype=a.dtype, soft_masks=soft, scale=scale, lr_hw=[h, w], frames=a.frames, rounds=a.rounds,
+    entry = dict(config=a.config, dtype=a.dtype, soft_masks=soft, soft_pair=bool(a.soft_pair), scale=scale, lr_hw=[h, w], frames=a.frames, rounds=a.rounds,
                  warmup=a.warmup, outputs_equal_to_b=same,
                  graph_replays=dict(dict(c=up_c.replays, d=up_d.replays),
                                     **{k + "_x8ens": up.replays for k, up in ens.items() if k != "b"}),
@@ -148,7 +153,8 @@ def main():
         if os.path.exists(a.out):
             with open(a.out) as fh:
                 data = json.load(fh)
-        data["%s_%s%s" % (a.config, a.dtype, ("" if soft is None else "_soft%g" % soft) + ("_x8ens" if ens else ""))] = entry
+        data["%s_%s%s" % (a.config, a.dtype, ("" if soft is None else "_soft%g" % soft) + ("_pair" if a.soft_pair else "") +
+                             ("_x8ens" if ens else ""))] = entry
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as fh:
             json.dump(data, fh, indent=1, sort_keys=True)
